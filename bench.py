@@ -11,13 +11,17 @@ x 20 dir, KL 256^2 screen, the antenna axis split over the --gpus N ranks
 ``--workload config3`` is configs[2] per GPU (weak scaling), ``config5``
 configs[4]'s per-GPU shard.  Only one-shot setup collectives.
 
-    python bench.py [--gpus N --steps K --warmup W]
+    python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR]
     torchrun --nproc-per-node N bench.py --gpus N ...
+    python bench.py --full      # + checks, side / child legs, FITS, CPU baseline
 
+A plain run sets up, warms up, times the K steps and prints the line;
+everything else the line can carry is measured only with ``--full``.
 Prints ONE JSON line on rank 0.
 """
 
 import argparse
+import contextlib
 import json
 import os
 import socket
@@ -57,6 +61,20 @@ def parse():
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--workload", default="config4", choices=sorted(WORKLOADS))
+    ap.add_argument("--full", action="store_true",
+                    help="everything beside the headline figure: the power "
+                         "sampler, the invariant and sampled-slot checks, the "
+                         "side legs, the child legs, the FITS wall-clock legs, "
+                         "the parity checks and the CPU baseline (each still "
+                         "switched off by its own --no-... option).  Without "
+                         "it a run sets up, warms up, times the steps, writes "
+                         "--dump-outputs and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed "
+                         "step computed (the arrays its caller receives) as "
+                         "DIR/<name>.npy, float32 / float64; outputs over a "
+                         "few MB as a fixed, seeded sample of slots (64 MB at "
+                         "most in all, see dump_outputs)")
     ap.add_argument("--ring-gb", type=float, default=16.0,
                     help="HBM ring for the output cubes (GiB)")
     ap.add_argument("--precise-sincos", action="store_true",
@@ -164,7 +182,7 @@ def parse():
                          "(voronoi_screen.py:132-216, sf_tess_fill), no fit")
     ap.add_argument("--no-parity", action="store_true",
                     help="skip the parity checks against the reference's golden "
-                         "outputs (tools/bench_parity.py; on by default, the "
+                         "outputs (tools/bench_parity.py; on with --full, the "
                          "line exits 3 when one fails)")
     ap.add_argument("--eval-only", action="store_true",
                     help="time only sf_kl_eval (profiling)")
@@ -189,9 +207,14 @@ def parse():
                          "self-launched ranks are killed")
     ap.add_argument("--no-child-legs", "--no-config5-leg", action="store_true",
                     dest="no_child_legs",
-                    help="skip the child-process legs of the default N = 1 run "
+                    help="skip the child-process legs of the default N = 1 --full run "
                          "(config 5, gain and tessellated on the config-3 shape)")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if not args.full:
+        # a plain run: the headline figure only
+        args.no_cpu_baseline = args.no_fits = args.no_side_legs = True
+        args.no_parity = args.no_child_legs = True
+    return args
 
 
 def log(msg):
@@ -1018,6 +1041,49 @@ def side_legs(ctx, torch, dev, stream, fit_stream, fit, evaluate, coef, bounds,
     return res
 
 
+DUMP_SEED = 20262
+DUMP_ARRAY_BYTES = 4 << 20   # per fit output (float64 on disk)
+DUMP_CUBE_BYTES = 16 << 20   # the output cubes (float32)
+
+
+def dump_outputs(torch, outdir, rank, arrays, out):
+    """--dump-outputs: what the last timed step left in its caller's arrays,
+    as ``outdir/<name>.npy`` (rank 0; other ranks ``<name>_rank<r>.npy``).
+
+    ``arrays``: the fit's per-slot outputs, [time][freq][station]... or one
+    value per slot; each is written whole when it fits DUMP_ARRAY_BYTES as
+    float64, else as a sample of its slots (rows) -- sorted indices drawn
+    without replacement by ``default_rng([DUMP_SEED, rows])``, so the same
+    arguments sample the same slots in every build.  float32 stays float32,
+    everything else (float64, the int32 orders and checksums) is written as
+    float64, which holds them exactly.  ``out``: the ring of output cubes
+    [ring][4][ny][nx]; the sampled ring entries, DUMP_CUBE_BYTES at most.
+    Nine arrays at most: under 64 MB in all."""
+    os.makedirs(outdir, exist_ok=True)
+    suffix = "" if rank == 0 else f"_rank{rank}"
+
+    def rows_of(a, rows, budget):
+        per_row = max(1, a.numel() // rows) * (4 if a.dtype == torch.float32 else 8)
+        n = int(max(1, min(rows, budget // per_row)))
+        a = a.reshape(rows, -1)
+        if n < rows:
+            idx = np.sort(np.random.default_rng([DUMP_SEED, rows]).choice(
+                rows, size=n, replace=False))
+            a = a[torch.as_tensor(idx, device=a.device)]
+        a = a.cpu().numpy()
+        a = a[:, 0] if a.shape[1] == 1 else a  # one value per slot: 1-D
+        return a if a.dtype == np.float32 else a.astype(np.float64)
+
+    for name, a in arrays.items():
+        rows = int(np.prod(a.shape[:3])) if a.dim() >= 3 else a.numel()
+        np.save(os.path.join(outdir, f"{name}{suffix}.npy"),
+                rows_of(a, rows, DUMP_ARRAY_BYTES))
+    cubes = rows_of(out, out.shape[0], DUMP_CUBE_BYTES)
+    np.save(os.path.join(outdir, f"out{suffix}.npy"),
+            cubes.reshape((-1,) + tuple(out.shape[1:])))
+    log(f"outputs of the last timed step written to {outdir}")
+
+
 def child_leg(extra, what, timeout_s=420, side=False, oracle=False):
     """One workload of BASELINE.json beside the config-4 line, in a child
     ``bench.py`` (its own device buffers; the parent holds its own and is
@@ -1028,7 +1094,7 @@ def child_leg(extra, what, timeout_s=420, side=False, oracle=False):
     import subprocess
     base = (["--cpu-workers", "8", "--cpu-fit-slots", "16", "--cpu-eval-slots", "2",
              "--no-cpu-reference-path"] if oracle else ["--no-cpu-baseline"])
-    cmd = [sys.executable, os.path.abspath(__file__), "--gpus", "1",
+    cmd = [sys.executable, os.path.abspath(__file__), "--gpus", "1", "--full",
            "--no-fits", "--no-child-legs",
            "--no-parity"] + base + ([] if side else ["--no-side-legs"]) + extra
     env = dict(os.environ, WORLD_SIZE="1", RANK="0", LOCAL_RANK="0")
@@ -1263,8 +1329,8 @@ def tess_steps(args, ctx, torch, dev, dist, world, rank, coll_dev, sol, setup,
         dist.barrier()
     torch.cuda.synchronize(dev)
     evs = []
-    sampler = PowerSampler(args.idents[rank].get("pci"))
-    with sampler:
+    sampler = PowerSampler(args.idents[rank].get("pci")) if args.full else None
+    with sampler or contextlib.nullcontext():
         t0 = time.perf_counter()
         for _ in range(args.steps):
             e0 = torch.cuda.Event(enable_timing=True)
@@ -1278,7 +1344,10 @@ def tess_steps(args, ctx, torch, dev, dist, world, rank, coll_dev, sol, setup,
             dist.barrier()
         elapsed = time.perf_counter() - t0
     local_elapsed = elapsed
-    power = sampler.summary(float(S) * 16 * P * args.steps, local_elapsed)
+    power = (sampler.summary(float(S) * 16 * P * args.steps, local_elapsed)
+             if sampler else None)
+    if args.dump_outputs and args.steps > 0:
+        dump_outputs(torch, args.dump_outputs, rank, {}, out)
     tmax = torch.tensor([elapsed], dtype=torch.float64, device=coll_dev)
     if dist.is_initialized():
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
@@ -1291,24 +1360,27 @@ def tess_steps(args, ctx, torch, dev, dist, world, rank, coll_dev, sol, setup,
     # smoothing: cos^2 + sin^2 = 1 (unit amplitudes), or with XX / YY
     # amplitudes the shared angle (Re XX Im YY - Im XX Re YY = 0 relative to
     # |XX| |YY|); and the first slot vs a gather
-    chk = out[: min(ring, 16)].double()
-    unit_err, check_name = None, "max_abs_cos2_plus_sin2_minus_1"
-    if args.smooth_pix == 0 and not args.tess_gain:
-        unit_err = float((chk[:, 0] ** 2 + chk[:, 1] ** 2 - 1).abs().max())
-    elif args.smooth_pix == 0:
-        cross = chk[:, 0] * chk[:, 3] - chk[:, 1] * chk[:, 2]
-        mag = (chk[:, 0].hypot(chk[:, 1]) * chk[:, 2].hypot(chk[:, 3])).clamp(min=1e-30)
-        unit_err, check_name = float((cross / mag).abs().max()), "max_rel_xx_yy_angle_cross"
-    # a slot of a station other than the reference (whose referenced phases
-    # are 0: every cell the same value, the labels untested)
-    k0 = 1 if setup["ref_ant"] == 0 and A > 1 else 0
-    one = torch.empty((1, 4, N, N), dtype=torch.float32, device=dev)
-    ctx.tess_fill(lab_d, N, N, ph[k0:k0 + 1], D, 1, one, smooth_pix=0.0, flags=flags)
-    p0 = ph[k0].cpu().numpy()
-    want = np.stack([np.cos(p0), np.sin(p0), np.cos(p0), np.sin(p0)]).astype(np.float32)
-    want = want[:, lab - 1]
-    got = one[0].cpu().numpy()
-    ulp = int(np.abs(got.view(np.int32).astype(np.int64) - want.view(np.int32)).max())
+    check, got, k0 = {}, None, 0
+    if args.full:
+        chk = out[: min(ring, 16)].double()
+        unit_err, check_name = None, "max_abs_cos2_plus_sin2_minus_1"
+        if args.smooth_pix == 0 and not args.tess_gain:
+            unit_err = float((chk[:, 0] ** 2 + chk[:, 1] ** 2 - 1).abs().max())
+        elif args.smooth_pix == 0:
+            cross = chk[:, 0] * chk[:, 3] - chk[:, 1] * chk[:, 2]
+            mag = (chk[:, 0].hypot(chk[:, 1]) * chk[:, 2].hypot(chk[:, 3])).clamp(min=1e-30)
+            unit_err, check_name = float((cross / mag).abs().max()), "max_rel_xx_yy_angle_cross"
+        # a slot of a station other than the reference (whose referenced phases
+        # are 0: every cell the same value, the labels untested)
+        k0 = 1 if setup["ref_ant"] == 0 and A > 1 else 0
+        one = torch.empty((1, 4, N, N), dtype=torch.float32, device=dev)
+        ctx.tess_fill(lab_d, N, N, ph[k0:k0 + 1], D, 1, one, smooth_pix=0.0, flags=flags)
+        p0 = ph[k0].cpu().numpy()
+        want = np.stack([np.cos(p0), np.sin(p0), np.cos(p0), np.sin(p0)]).astype(np.float32)
+        want = want[:, lab - 1]
+        got = one[0].cpu().numpy()
+        ulp = int(np.abs(got.view(np.int32).astype(np.int64) - want.view(np.int32)).max())
+        check = {check_name: unit_err, "slot0_max_ulp_vs_numpy_gather": ulp}
     if rank == 0:
         bytes_launch = S * (16 * P + 8 * D)
         achieved = bytes_launch / launch_s / 1e9
@@ -1349,8 +1421,7 @@ def tess_steps(args, ctx, torch, dev, dist, world, rank, coll_dev, sol, setup,
                          "bytes_per_launch": bytes_launch,
                          "launch_ms": launch_s * 1e3},
             "power": power,
-            "check": {check_name: unit_err,
-                      "slot0_max_ulp_vs_numpy_gather": ulp},
+            "check": check,
             "dist": dist_info,
         }
         failed = False
@@ -1708,8 +1779,8 @@ def main():
         dist.barrier()
     torch.cuda.synchronize(dev)
     log(f"timed: {args.steps} steps")
-    sampler = PowerSampler(args.idents[rank].get("pci"))
-    with sampler:
+    sampler = PowerSampler(args.idents[rank].get("pci")) if args.full else None
+    with sampler or contextlib.nullcontext():
         t0 = time.perf_counter()
         ev = run_steps(args.steps)
         torch.cuda.synchronize(dev)
@@ -1717,7 +1788,20 @@ def main():
             dist.barrier()
         elapsed = time.perf_counter() - t0
     local_elapsed = elapsed
-    power = sampler.summary(float(S) * 16 * P * args.steps, local_elapsed)
+    power = (sampler.summary(float(S) * 16 * P * args.steps, local_elapsed)
+             if sampler else None)
+    if args.dump_outputs and args.steps > 0:
+        b = (args.steps - 1) % n_sets  # the coefficient set of the last step
+        arrays = {"coef": coef_sets[b], "resid": resid, "w_out": w_out,
+                  "order_out": order_out}
+        if gain:
+            # the amplitude fit's outputs, pols stacked along the station axis
+            arrays.update(amp_coef=amp_sets[b][0], amp_resid=amp["resid"],
+                          amp_w_out=amp["w_out"], amp_order_out=amp["orders"])
+        if checksum:
+            # accumulated over the warmup and timed evaluations of each slot
+            arrays["slot_sums"] = slot_sums
+        dump_outputs(torch, args.dump_outputs, rank, arrays, out)
     ctx.set_stream(stream.cuda_stream)
     fit_stats = ctx.fit_stats() if not args.eval_only else {}
     # per-step stage sums; per-launch eval duration for the roofline
@@ -1738,20 +1822,23 @@ def main():
     # invariant of its planes -- phase screens cos^2 + sin^2 = 1; gain screens
     # Re XX / Im XX and Re YY / Im YY share an angle, so
     # Re XX * Im YY - Im XX * Re YY = 0 relative to |XX| |YY|
-    chk = out[: min(ring, 64)].double()
-    if gain:
-        cross = chk[:, 0] * chk[:, 3] - chk[:, 1] * chk[:, 2]
-        mag = (chk[:, 0].hypot(chk[:, 1]) * chk[:, 2].hypot(chk[:, 3])).clamp(min=1e-30)
-        check_name = "max_rel_xx_yy_angle_cross"
-        unit_err = float((cross / mag).abs().max())
-    else:
-        check_name = "max_abs_cos2_plus_sin2_minus_1"
-        unit_err = float((chk[:, 0] ** 2 + chk[:, 1] ** 2 - 1).abs().max())
-    sampled = sampled_slots_check(
-        ctx, torch, dev, setup, coef.reshape(-1, D), N, flags, slot_sums,
-        args.warmup + args.steps, not args.precise_sincos,
-        cxx=amp["coef"][0].reshape(-1, D) if gain else None,
-        cyy=amp["coef"][1].reshape(-1, D) if gain else None)
+    check = {}
+    if args.full:
+        chk = out[: min(ring, 64)].double()
+        if gain:
+            cross = chk[:, 0] * chk[:, 3] - chk[:, 1] * chk[:, 2]
+            mag = (chk[:, 0].hypot(chk[:, 1]) * chk[:, 2].hypot(chk[:, 3])).clamp(min=1e-30)
+            check_name = "max_rel_xx_yy_angle_cross"
+            unit_err = float((cross / mag).abs().max())
+        else:
+            check_name = "max_abs_cos2_plus_sin2_minus_1"
+            unit_err = float((chk[:, 0] ** 2 + chk[:, 1] ** 2 - 1).abs().max())
+        sampled = sampled_slots_check(
+            ctx, torch, dev, setup, coef.reshape(-1, D), N, flags, slot_sums,
+            args.warmup + args.steps, not args.precise_sincos,
+            cxx=amp["coef"][0].reshape(-1, D) if gain else None,
+            cyy=amp["coef"][1].reshape(-1, D) if gain else None)
+        check = {check_name: unit_err, "sampled_slots": sampled}
 
     side = {}
     if not args.no_side_legs and not args.eval_only:
@@ -1854,7 +1941,7 @@ def main():
                                       "coefficient sets" % (n_chunks, n_sets))},
             "fit_stats": fit_stats,
             "power": power,
-            "check": {check_name: unit_err, "sampled_slots": sampled},
+            "check": check,
             "dist": dist_info,
         }
         if side:

@@ -15,7 +15,7 @@ REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 def _bench(*args):
     cmd = [sys.executable, os.path.join(REPO, "bench.py"), "--workload", "tiny",
-           "--steps", "3", "--warmup", "1", "--no-cpu-baseline", "--no-side-legs",
+           "--full", "--steps", "3", "--warmup", "1", "--no-cpu-baseline", "--no-side-legs",
            "--no-fits", "--no-child-legs", *args]
     if "--cpu-baseline" in args:
         cmd.remove("--cpu-baseline")
@@ -66,6 +66,60 @@ def test_bench_line_carries_parity():
     assert par["config1"]["screens_png"]["mismatched_tessellated"] == 0
     assert par["config2"]["cube_from"].startswith("make_aterm_image")
     assert line["library"]["sha16"]
+
+
+def _plain(tmp_path, name, steps, *extra):
+    d = tmp_path / name
+    cmd = [sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "1", "--workload",
+           "tiny", "--steps", str(steps), "--warmup", "1", "--dump-outputs", str(d), *extra]
+    r = subprocess.run(cmd, capture_output=True, text=True, timeout=300, cwd=REPO)
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [x for x in r.stdout.splitlines() if x.startswith("{")]
+    assert len(lines) == 1, r.stdout[-2000:]
+    return json.loads(lines[0]), d
+
+
+@pytest.mark.gpu
+def test_plain_run_is_lean_and_dumps_its_outputs(tmp_path):
+    """A plain run (no --full) times the steps and prints the headline line
+    without the checks, legs and baselines; --dump-outputs writes the last
+    step's outputs as float32 / float64 .npy files, equal from run to run
+    and whatever the number of steps (every step computes the same batch) --
+    but for the streamed checksums, which count every evaluation: (warmup +
+    steps) x one evaluation's, modulo 2^32."""
+    import numpy as np
+    two, d2 = _plain(tmp_path, "two", 2, "--checksum", "on")
+    three, d3 = _plain(tmp_path, "three", 3, "--checksum", "on")
+    base = json.load(open(os.path.join(REPO, "BASELINE.json")))
+    for line, steps in ((two, 2), (three, 3)):
+        assert line["metric"] == base["metric"] and line["unit"] == "screen-slots/s"
+        assert line["steps"] == steps and line["warmup"] == 1
+        assert line["value"] > 0 and line["ms_per_step"] > 0
+        assert line["higher_is_better"] is True and line["dtype"] == "f64"
+        # 80 x 4 x 2 slots per step
+        assert line["value"] == pytest.approx(640 / line["ms_per_step"] * 1e3, rel=1e-9)
+        assert line["check"] == {} and line["power"] is None
+        for k in ("cpu_baseline", "side_legs", "fits_wallclock", "parity"):
+            assert k not in line
+    names = sorted(p.name for p in d2.iterdir())
+    assert names == ["coef.npy", "order_out.npy", "out.npy", "resid.npy", "slot_sums.npy",
+                     "w_out.npy"]
+    assert names == sorted(p.name for p in d3.iterdir())
+    total = 0
+    for n in names:
+        a, b = np.load(d2 / n), np.load(d3 / n)
+        assert a.dtype in (np.float32, np.float64) and a.shape == b.shape
+        total += a.nbytes
+        if n != "slot_sums.npy":
+            np.testing.assert_array_equal(a, b, err_msg=n)
+    assert total <= 64 << 20
+    assert np.load(d2 / "coef.npy").shape == (640, 7)
+    assert np.load(d2 / "out.npy").shape == (640, 4, 32, 32)
+    assert np.load(d2 / "w_out.npy").dtype == np.float32
+    s2 = np.load(d2 / "slot_sums.npy").astype(np.int64)
+    s3 = np.load(d3 / "slot_sums.npy").astype(np.int64)
+    assert s2.any()
+    np.testing.assert_array_equal((4 * s2) % 2 ** 32, (3 * s3) % 2 ** 32)
 
 
 def _assert_contract(line, steps=3, warmup=1):
@@ -132,7 +186,7 @@ def test_full_size_workload_fit_and_eval_vs_oracle(workload):
     <= 1e-8), the sampled slots' evaluation against an fp64 restatement of
     kl_screen.py:444-449 and their streamed checksums."""
     cmd = [sys.executable, os.path.join(REPO, "bench.py"), "--workload", workload,
-           "--steps", "1", "--warmup", "0", "--no-side-legs", "--no-fits",
+           "--full", "--steps", "1", "--warmup", "0", "--no-side-legs", "--no-fits",
            "--no-child-legs", "--no-parity", "--cpu-workers", "8", "--cpu-fit-slots", "16",
            "--cpu-eval-slots", "2", "--no-cpu-reference-path"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=REPO)

@@ -186,6 +186,63 @@ def test_child_leg_parity_fails_on_a_broken_leg():
     assert bench.child_leg_parity({"config5": good["config5"]}, line) is False
 
 
+def test_plain_run_switches_off_everything_but_the_headline(monkeypatch):
+    """Without --full every extra leg is off; with it each keeps its own
+    --no-... switch."""
+    sys.path.insert(0, REPO)
+    import bench
+    extras = ("no_cpu_baseline", "no_fits", "no_side_legs", "no_parity", "no_child_legs")
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "7",
+                                      "--warmup", "3"])
+    a = bench.parse()
+    assert not a.full and a.dump_outputs is None and (a.steps, a.warmup) == (7, 3)
+    assert all(getattr(a, k) for k in extras)
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--no-fits",
+                                      "--dump-outputs", "somewhere"])
+    a = bench.parse()
+    assert a.full and a.no_fits and a.dump_outputs == "somewhere"
+    assert not any(getattr(a, k) for k in extras if k != "no_fits")
+
+
+def test_dump_outputs_writes_whole_arrays_or_fixed_samples(tmp_path, monkeypatch):
+    """bench.dump_outputs: small arrays whole, large ones as a sample of
+    their slots that depends only on the seed and the slot count; float32
+    stays float32, float64 and integers become float64 (exact)."""
+    import numpy as np
+    import torch
+    sys.path.insert(0, REPO)
+    import bench
+    monkeypatch.setattr(bench, "DUMP_ARRAY_BYTES", 1 << 10)
+    monkeypatch.setattr(bench, "DUMP_CUBE_BYTES", 3 * 4 * 5 * 6 * 4)
+    g = torch.Generator().manual_seed(3)
+    coef = torch.randn((6, 5, 4, 7), generator=g, dtype=torch.float64)     # 120 slots
+    w = torch.rand((6, 5, 4, 7), generator=g, dtype=torch.float32)
+    order = torch.arange(120, dtype=torch.int32).reshape(6, 5, 4)          # 960 B as f64
+    sums = torch.tensor([-2 ** 31, 2 ** 31 - 1, 5], dtype=torch.int32)
+    out = torch.randn((10, 4, 5, 6), generator=g, dtype=torch.float32)
+    arrays = {"coef": coef, "w_out": w, "order_out": order, "slot_sums": sums}
+    for name in ("a", "b"):
+        bench.dump_outputs(torch, str(tmp_path / name), 0, arrays, out)
+    got = {p.name[:-4]: np.load(p) for p in (tmp_path / "a").iterdir()}
+    assert sorted(got) == ["coef", "order_out", "out", "slot_sums", "w_out"]
+    for k, v in got.items():
+        np.testing.assert_array_equal(v, np.load(tmp_path / "b" / f"{k}.npy"))
+    idx = np.sort(np.random.default_rng([bench.DUMP_SEED, 120]).choice(120, 18, replace=False))
+    assert got["coef"].dtype == np.float64 and got["coef"].shape == (18, 7)    # 1024 // 56
+    np.testing.assert_array_equal(got["coef"], coef.reshape(120, 7).numpy()[idx])
+    idx = np.sort(np.random.default_rng([bench.DUMP_SEED, 120]).choice(120, 36, replace=False))
+    assert got["w_out"].dtype == np.float32
+    np.testing.assert_array_equal(got["w_out"], w.reshape(120, 7).numpy()[idx])
+    np.testing.assert_array_equal(got["order_out"], np.arange(120.0))
+    np.testing.assert_array_equal(got["slot_sums"], [-2.0 ** 31, 2.0 ** 31 - 1, 5.0])
+    idx = np.sort(np.random.default_rng([bench.DUMP_SEED, 10]).choice(10, 3, replace=False))
+    assert got["out"].dtype == np.float32
+    np.testing.assert_array_equal(got["out"], out.numpy()[idx])
+    # another rank writes beside rank 0's files
+    bench.dump_outputs(torch, str(tmp_path / "a"), 2, {"coef": coef}, out)
+    assert (tmp_path / "a" / "coef_rank2.npy").exists()
+
+
 def test_pick_schedule_defaults():
     """Phase screens: one chunk, one coefficient set (at any N); gain: two
     sets over a multi-step run (fit of step k+1 beside the eval of step k)."""

@@ -152,18 +152,20 @@ def test_writer_many_members_and_types(tmp_path):
         assert f["scalar"].shape == () and f["scalar"][()] == np.float32(3.5)
 
 
-REF_H5 = "/root/reference/resources/solutions.h5"
+REF_H5_GZ = os.path.join(H5, "reference_solutions.h5.gz")
 
 
-@pytest.mark.skipif(not os.path.exists(REF_H5),
-                    reason="the reference tree is only present in the build container")
-def test_reference_solutions_h5_reads_as_fixture():
+def test_reference_solutions_h5_reads_as_fixture(tmp_path):
     """The reference's own resources/solutions.h5 (the file its tests feed
-    make_aterm_image, written by DP3 / PyTables) read by this build's HDF5
-    reader equals the golden fixture the reference itself produced from it
-    (make_golden.py read it with h5py)."""
+    make_aterm_image, written by DP3 / PyTables; stored here gzipped, byte
+    for byte) read by this build's HDF5 reader equals the golden fixture the
+    reference itself produced from it (make_golden.py read it with h5py)."""
+    import gzip
     g = load_golden("fixture_kl")
-    ss = H5parm(REF_H5).get_solset("sol000")
+    ref_h5 = str(tmp_path / "solutions.h5")
+    with gzip.open(REF_H5_GZ, "rb") as src, open(ref_h5, "wb") as dst:
+        dst.write(src.read())
+    ss = H5parm(ref_h5).get_solset("sol000")
     st = ss.get_soltab("phase000")
     assert st.get_axes_names() == ["time", "freq", "ant", "dir"]
     np.testing.assert_array_equal(st.val, g["val"])

@@ -1,4 +1,4 @@
-"""Parity evidence carried by every bench.py line (``parsed.parity``).
+"""Parity evidence carried by every ``bench.py --full`` line (``parsed.parity``).
 
 Runs outside the timed region, on the product path (the HIP library through
 its C ABI and the drop-in ``make_aterm_image``), against the committed
