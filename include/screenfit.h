@@ -12,6 +12,10 @@
  *   sf_kl_fit     <- stationscreen.run -> _process_single_freq ->
  *                    _process_station -> _fit_screen
  *                    (stationscreen.py:858-1161, 785-855, 597-782, 433-594)
+ *   sf_set_piercepoints <- the piercepoint / r_0 / beta attributes that
+ *                    KLScreen.make_matrix reads from the screen soltab and
+ *                    hands to calculate_kl_screen (kl_screen.py:228-261,
+ *                    411-449): the evaluation-only geometry, no eigen-basis
  *   sf_set_grid   <- KLScreen.make_matrix coordinate block
  *                    (kl_screen.py:228-261)
  *   sf_kl_eval    <- KLScreen.make_matrix + calculate_kl_screen + the NaN
@@ -54,7 +58,11 @@ extern "C" {
 #define SF_EIO (-5)
 #define SF_ENODEV (-19)
 
-#define SF_MAX_DIR 60 /* directions per slot (one wavefront lane each; LDS-bound) */
+#define SF_MAX_DIR 60 /* directions per slot of sf_set_basis / sf_kl_fit (one
+                         wavefront lane each; LDS-bound) */
+/* directions per slot of the pixel side: sf_set_piercepoints, sf_set_grid,
+ * sf_kl_eval / _gain / _sums and sf_tess_fill */
+#define SF_MAX_EVAL_DIR 128
 
 /* screen types of stationscreen.run (stationscreen.py:922-928) */
 #define SF_SCREEN_PHASE 0
@@ -109,7 +117,8 @@ int sf_device_cus(sf_ctx* ctx, int* n_cu);
  * the same values): AUTO (default), TILE = register-tile stores (4 slots x
  * 256 B per store instruction; always used for fp64 sincos and gain
  * screens), LDS4 / LDS8 / LDS16 = LDS-staged stores with 1 / 2 / 4 KiB
- * contiguous runs per (slot, plane). */
+ * contiguous runs per (slot, plane).  Ignored for D > 60
+ * (SF_EVAL_KERNEL_WIDE). */
 #define SF_OPT_EVAL_KERNEL 2
 /* SF_OPT_EVAL_MAX_BLOCKS caps the workgroups of an evaluation launch (0 =
  * the dispatch limit); each workgroup then walks several (pixel block, slot
@@ -120,7 +129,7 @@ int sf_device_cus(sf_ctx* ctx, int* n_cu);
 #define SF_OPT_FIT_PACK 4
 /* SF_OPT_EVAL_KS_PAD = n (0..3) runs the evaluation contraction with n extra
  * all-zero k-steps of 4 directions (same values; tuning / diagnostics). */
-#define SF_OPT_EVAL_KS_PAD 5
+#define SF_OPT_EVAL_KS_PAD 5 /* (ignored for D > 60) */
 /* SF_OPT_EVAL_SLEEP = n: LDS-staged evaluation waves sleep n x 64 cycles
  * after each 16-slot contraction (store-throttling experiments; default 0). */
 #define SF_OPT_EVAL_SLEEP 6
@@ -180,7 +189,7 @@ int sf_device_cus(sf_ctx* ctx, int* n_cu);
  * rounding of the reduced phase (up to 2^-26 turn); it runs in the register
  * tile, the SHB tile (pixel digits shared in LDS by 4 waves) and the
  * LDS-staged kernels alike (same bits; sf_get_eval_kernel /
- * sf_get_eval_contraction say which). */
+ * sf_get_eval_contraction say which).  Ignored for D > 60 (fp64). */
 #define SF_OPT_EVAL_INT 15
 /* SF_OPT_EVAL_WG_WAVES: waves per workgroup of the integer-digit register
  * tile -- 4 (0 = default: 256 pixels, 1 KiB store runs per (slot, plane)) or
@@ -188,7 +197,8 @@ int sf_device_cus(sf_ctx* ctx, int* n_cu);
  * (SF_EVAL_KERNEL_TILE / TILE3) running the integer-digit contraction
  * (sf_get_eval_contraction == 1); the fp64 contraction, the LDS-staged
  * kernels and SF_EVAL_KERNEL_SHB always run 4-wave workgroups and ignore it
- * (the Python binding's eval_kernel() names the 8-wave variant when it runs). */
+ * (the Python binding's eval_kernel() names the 8-wave variant when it runs).
+ * Ignored for D > 60. */
 #define SF_OPT_EVAL_WG_WAVES 16
 /* SF_OPT_FIT_EIG_WAVES: waves per flagged-direction mask of the subset-basis
  * Jacobi in sf_kl_fit -- 1..4 (0 = default: 3).  Every count writes the same
@@ -214,9 +224,18 @@ int sf_device_cus(sf_ctx* ctx, int* n_cu);
 #define SF_EVAL_KERNEL_LDS16H 6
 #define SF_EVAL_KERNEL_TILE3 7 /* register tile at 3 waves per SIMD */
 #define SF_EVAL_KERNEL_SHB 8 /* register tile, Cpix (or its digits) shared in LDS by 4 waves */
+/* D > 60 (16..32 k-steps, after sf_set_piercepoints): the wide kernel
+ * (kl_eval_wide.hip) -- run-time k-loop, Cpix of a 64-pixel block in LDS,
+ * fp64 contraction (SF_EVAL_CONTRACTION_F64), exact phase reduction.  It is
+ * the only kernel there: SF_OPT_EVAL_KERNEL, SF_OPT_EVAL_INT,
+ * SF_OPT_EVAL_KS_PAD and SF_OPT_EVAL_WG_WAVES are ignored above 60 directions
+ * (SF_OPT_EVAL_MAX_BLOCKS, _GROUPS, _BANDS and _XCD_MAP are honoured).  As a
+ * value of SF_OPT_EVAL_KERNEL it is accepted and means AUTO for D <= 60. */
+#define SF_EVAL_KERNEL_WIDE 9
 /* The evaluation kernel sf_kl_eval (gain = 0) or sf_kl_eval_gain (gain = 1)
  * runs for the current grid and these flags on a 16-byte aligned output
- * (one of SF_EVAL_KERNEL_TILE / _LDS4 / _LDS8 / _LDS16). */
+ * (one of SF_EVAL_KERNEL_TILE / _LDS4 / _LDS8 / _LDS16 ..., or
+ * SF_EVAL_KERNEL_WIDE for every call with D > 60). */
 int sf_get_eval_kernel(sf_ctx* ctx, int gain, unsigned flags, int* kernel);
 /* The contraction of that evaluation: SF_EVAL_CONTRACTION_F64 (fp64 MFMAs) or
  * SF_EVAL_CONTRACTION_I8_DIGITS (the integer-digit contraction,
@@ -240,9 +259,26 @@ int sf_copy_d2h(sf_ctx* ctx, void* dst_host, const void* src_dev, size_t bytes);
  */
 int sf_set_basis(sf_ctx* ctx, const double* pp_host, int D, double r0,
                  double beta);
-/* Copy the device basis back (host [D][D] each; any pointer may be NULL). */
+/* Copy the device basis back (host [D][D] each; any pointer may be NULL).
+ * SF_EINVAL on a context whose geometry came from sf_set_piercepoints. */
 int sf_get_basis(sf_ctx* ctx, double* c_host, double* pinv_c_host,
                  double* u_host, double* eig_host);
+
+/*
+ * Evaluation-only geometry: the D piercepoints (host, [D][3] float64), r0
+ * and beta that sf_set_grid and sf_kl_eval* read -- the pixel basis
+ * Cpix[p][d] = -(|pp_d - (x_p, y_p, 0)|^2 / r0^2)^(beta/2) / 2 of
+ * calculate_kl_screen (kl_screen.py:411-449) needs nothing else.
+ * 1 <= D <= SF_MAX_EVAL_DIR, r0 > 0.  No eigen-basis is computed or
+ * allocated: on such a context sf_kl_fit and sf_get_basis return SF_EINVAL
+ * until sf_set_basis is called (which makes it a full context again).  Like
+ * sf_set_basis it invalidates the pixel grid; a failed call leaves the
+ * context usable (no geometry, as after sf_create).  For D <= SF_MAX_DIR the
+ * evaluation is bit for bit the one after sf_set_basis with the same
+ * arguments.
+ */
+int sf_set_piercepoints(sf_ctx* ctx, const double* pp_host, int D, double r0,
+                        double beta);
 
 /*
  * Batched KL least-squares fit of all T*F*A slots (one scalar-phase or tec
@@ -254,7 +290,8 @@ int sf_get_basis(sf_ctx* ctx, double* c_host, double* pinv_c_host,
  * coef): coef [T][F][A][D] float64 (the "phase_screen000" values),
  * resid [T][F][A][D] float64, w_out [T][F][A][D] float32 (weights after
  * outlier flagging), order_out [T][F][A] int32 (orders, the weights of the
- * "...resid" soltab).  Requires sf_set_basis with the same D.
+ * "...resid" soltab).  Requires sf_set_basis with the same D
+ * (sf_set_piercepoints does not serve: SF_EINVAL).
  */
 int sf_kl_fit(sf_ctx* ctx, const double* phase, const float* weight, int T,
               int F, int A, const int* station_order_host,
@@ -283,7 +320,8 @@ int sf_get_fit_pool(sf_ctx* ctx, uint64_t* masks_host, double* entries_host,
  * Pixel grid of the a-term image: X[nx], Y[ny] screen coordinates of the
  * diagonal pixels (kl_screen.py:247-259, quirk Q8: pixel (y=j, x=i) is
  * evaluated at (X[i], Y[j])).  Builds the [nx*ny][D] pixel basis on the
- * device in MFMA fragment order.  Requires sf_set_basis first.
+ * device in MFMA fragment order.  Requires sf_set_basis or
+ * sf_set_piercepoints first (D <= SF_MAX_EVAL_DIR).
  */
 int sf_set_grid(sf_ctx* ctx, const double* x_host, int nx,
                 const double* y_host, int ny);
@@ -294,6 +332,8 @@ int sf_set_grid(sf_ctx* ctx, const double* x_host, int nx,
  * float32 to out[(s % ring_slots)][4][ny][nx] (device).  ring_slots >= S
  * writes every slot to its own place; smaller rings let a benchmark stream
  * an output volume larger than HBM.  coef: device [S][D] float64.
+ * D <= SF_MAX_EVAL_DIR (above SF_MAX_DIR: SF_EVAL_KERNEL_WIDE); the same
+ * holds for sf_kl_eval_gain and sf_kl_eval_sums.
  */
 int sf_kl_eval(sf_ctx* ctx, const double* coef, int64_t S, float* out,
                int64_t ring_slots, unsigned flags);
@@ -324,7 +364,8 @@ int sf_kl_eval_sums(sf_ctx* ctx, const double* coef_phase,
  * direction whose cell contains it, then (smooth_pix > 0) apply the Gaussian
  * of Screen.write.  Replaces VoronoiScreen.make_matrix + the smoothing loop
  * (voronoi_screen.py:132-216, screen.py:353-362).  Device inputs: labels
- * [ny][nx] int32 in 1..D (the template of make_rasertize_template), phase
+ * [ny][nx] int32 in 1..D, D <= SF_MAX_EVAL_DIR (the template of
+ * make_rasertize_template), phase
  * [S][D] float64 (already referenced), amp_xx / amp_yy [S][D] float64 or NULL
  * (phase-only: amplitude 1).  Output as sf_kl_eval.  smooth_pix <= 6 runs
  * fused in one LDS-tiled kernel; larger values (any sigma, as scipy) gather

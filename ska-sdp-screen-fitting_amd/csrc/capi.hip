@@ -169,7 +169,7 @@ int sf_set_option(sf_ctx* ctx, int option, int value) {
       ctx->force_general = value != 0;
       return SF_OK;
     case SF_OPT_EVAL_KERNEL:
-      SF_REQUIRE(value >= SF_EVAL_KERNEL_AUTO && value <= SF_EVAL_KERNEL_SHB,
+      SF_REQUIRE(value >= SF_EVAL_KERNEL_AUTO && value <= SF_EVAL_KERNEL_WIDE,
                  SF_EINVAL, "sf_set_option: unknown evaluation kernel");
       ctx->eval_kernel = value;
       return SF_OK;
@@ -324,6 +324,7 @@ int sf_set_basis(sf_ctx* ctx, const double* pp, int D, double r0,
   // invalidate basis and grid until the new basis is complete: a failure
   // below must not leave a context whose D points at freed buffers
   ctx->D = 0;
+  ctx->has_basis = 0;
   ctx->nx = ctx->ny = 0;
   ctx->n_pix = 0;
   SF_TRY(dev_alloc(&ctx->d_pp, (size_t)3 * D));
@@ -344,12 +345,40 @@ int sf_set_basis(sf_ctx* ctx, const double* pp, int D, double r0,
     rc = SF_EIO;
   }
   if (rc != SF_OK) ctx->D = 0;
+  ctx->has_basis = rc == SF_OK;
   return rc;
+}
+
+int sf_set_piercepoints(sf_ctx* ctx, const double* pp, int D, double r0,
+                        double beta) {
+  SF_REQUIRE(ctx && pp, SF_EINVAL, "sf_set_piercepoints: bad argument");
+  SF_REQUIRE(D >= 1 && D <= SF_MAX_EVAL_DIR, SF_EINVAL,
+             "sf_set_piercepoints: D out of range [1, SF_MAX_EVAL_DIR]");
+  SF_REQUIRE(r0 > 0.0, SF_EINVAL, "sf_set_piercepoints: r0 must be > 0");
+  SF_HIP(hipSetDevice(ctx->device));
+  SF_HIP(hipStreamSynchronize(ctx->stream));
+  // as sf_set_basis: no geometry and no grid until the new one is complete;
+  // the eigen-basis buffers of an earlier sf_set_basis are not this D's
+  ctx->D = 0;
+  ctx->has_basis = 0;
+  ctx->nx = ctx->ny = 0;
+  ctx->n_pix = 0;
+  SF_TRY(dev_alloc(&ctx->d_pp, (size_t)3 * D));
+  SF_HIP(hipMemcpy(ctx->d_pp, pp, sizeof(double) * 3 * D,
+                   hipMemcpyHostToDevice));
+  for (int i = 0; i < 3 * D; ++i) ctx->h_pp[i] = pp[i];
+  ctx->D = D;
+  ctx->r0 = r0;
+  ctx->beta = beta;
+  return SF_OK;
 }
 
 int sf_get_basis(sf_ctx* ctx, double* c, double* pinv, double* u,
                  double* eig) {
   SF_REQUIRE(ctx && ctx->D > 0, SF_EINVAL, "sf_get_basis: no basis set");
+  SF_REQUIRE(ctx->has_basis, SF_EINVAL,
+             "sf_get_basis: the context holds piercepoints only "
+             "(sf_set_piercepoints); call sf_set_basis");
   SF_HIP(hipSetDevice(ctx->device));
   SF_HIP(hipStreamSynchronize(ctx->stream));
   const size_t n = (size_t)ctx->D * ctx->D * sizeof(double);
@@ -366,6 +395,9 @@ int sf_kl_fit(sf_ctx* ctx, const double* phase, const float* weight, int T,
               int F, int A, const int* st_order, const sf_fit_params* p,
               double* coef, double* resid, float* w_out, int32_t* order_out) {
   SF_REQUIRE(ctx && ctx->D > 0, SF_EINVAL, "sf_kl_fit: call sf_set_basis first");
+  SF_REQUIRE(ctx->has_basis, SF_EINVAL,
+             "sf_kl_fit: the context holds piercepoints only "
+             "(sf_set_piercepoints); the fit needs sf_set_basis");
   SF_REQUIRE(phase && weight && st_order && p && coef, SF_EINVAL,
              "sf_kl_fit: NULL argument");
   SF_REQUIRE(T >= 1 && F >= 1 && A >= 1, SF_EINVAL,
@@ -444,7 +476,8 @@ int sf_get_fit_pool(sf_ctx* ctx, uint64_t* masks_host, double* entries_host,
 
 int sf_set_grid(sf_ctx* ctx, const double* x, int nx, const double* y,
                 int ny) {
-  SF_REQUIRE(ctx && ctx->D > 0, SF_EINVAL, "sf_set_grid: call sf_set_basis first");
+  SF_REQUIRE(ctx && ctx->D > 0, SF_EINVAL,
+             "sf_set_grid: call sf_set_basis or sf_set_piercepoints first");
   SF_REQUIRE(x && y && nx >= 1 && ny >= 1, SF_EINVAL, "sf_set_grid: bad grid");
   for (int i = 0; i < nx; ++i)
     SF_REQUIRE(std::isfinite(x[i]), SF_EINVAL, "sf_set_grid: non-finite x coordinate");
@@ -503,12 +536,13 @@ int sf_set_grid(sf_ctx* ctx, const double* x, int nx, const double* y,
       cmax = std::isfinite(c) ? std::fmax(cmax, c) : HUGE_VAL;
     }
   }
-  // the integer-digit contraction (D >= 45): rint(Cpix * 2^36) must fit 6
+  // the integer-digit contraction (D = 45..60): rint(Cpix * 2^36) must fit 6
   // balanced base-256 digits (|.| < 2^46.99); 2^46.9 leaves the margin, and
   // kl_cdig_kernel reports any value that still does not fit
   ctx->dig_ok = 0;
   int* dbad = nullptr;
-  if (rc == SF_OK && ctx->ksteps >= 12 && std::isfinite(cmax) &&
+  if (rc == SF_OK && ctx->ksteps >= 12 && ctx->ksteps <= sf::kEvalMaxKS &&
+      std::isfinite(cmax) &&
       cmax * 68719476736.0 < std::ldexp(1.0, 46) * 1.86) {
     // (no memory for the digits: the fp64 contraction serves, not an error)
     if (dev_alloc(&ctx->d_cdig, (size_t)ctx->n_pix_blocks * sf::kEvalWaves *
@@ -631,7 +665,7 @@ int sf_tess_fill(sf_ctx* ctx, const int32_t* labels, int nx, int ny,
                  const double* amp_yy, int D, int64_t S, float* out,
                  int64_t ring, double smooth_pix, unsigned flags) {
   SF_REQUIRE(ctx && labels && phase && out, SF_EINVAL, "sf_tess_fill: NULL argument");
-  SF_REQUIRE(nx >= 1 && ny >= 1 && D >= 1 && D <= 64 && S >= 0 && ring >= 1 &&
+  SF_REQUIRE(nx >= 1 && ny >= 1 && D >= 1 && D <= SF_MAX_EVAL_DIR && S >= 0 && ring >= 1 &&
                  ring <= INT32_MAX,
              SF_EINVAL, "sf_tess_fill: bad shape");
   SF_REQUIRE(smooth_pix >= 0.0 && smooth_pix <= 1e4, SF_EINVAL,

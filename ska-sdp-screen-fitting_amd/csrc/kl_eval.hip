@@ -143,12 +143,16 @@ int launch_cdig(sf_ctx* ctx, const double* d_x, const double* d_y, int* d_bad) {
 // Kernel sf_kl_eval runs for this context, output alignment and flags.
 int pick_eval_kernel(const sf_ctx* ctx, bool gain, unsigned flags,
                      bool out_aligned16) {
+  // D > 60: one kernel for everything (kl_eval_wide.hip)
+  if (ctx->ksteps > kEvalMaxKS) return SF_EVAL_KERNEL_WIDE;
   // the LDS-staged kernel covers phase screens with the fast (hardware) sincos
   // epilogue and float4-aligned output; everything else (fp64 sincos, gain
   // screens, odd grids) takes the register-tile kernel
   const bool lds_ok = !gain && (flags & SF_EVAL_FAST_SINCOS) &&
                       (ctx->n_pix % 4 == 0) && out_aligned16;
-  const int opt = ctx->eval_kernel;
+  // (the wide kernel serves D > 60 only: asked for below that, the auto choice)
+  const int opt = ctx->eval_kernel == SF_EVAL_KERNEL_WIDE ? SF_EVAL_KERNEL_AUTO
+                                                          : ctx->eval_kernel;
   if (gain) {
     // round 6: gain screens on the LDS-staged kernels whose three-plane tile
     // fits LDS (LDS16's 1024-pixel run does not: LDS16H instead), fast
@@ -205,6 +209,8 @@ int launch_eval(sf_ctx* ctx, const double* coef, const double* cxx,
     return SF_EINVAL;
   }
   if (ring > S) ring = S > 0 ? S : 1;
+  if (ctx->ksteps > kEvalMaxKS)
+    return launch_eval_wide(ctx, coef, cxx, cyy, S, out, ring, flags, sums);
   // zero k-step padding (SF_OPT_EVAL_KS_PAD) only for the LDS-staged
   // kernels, which take the real k-step count for their Cpix indexing
   const int v = pick_eval_kernel(ctx, cxx != nullptr, flags,

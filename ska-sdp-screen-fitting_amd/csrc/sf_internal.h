@@ -45,8 +45,10 @@ constexpr int kDigits = 6;
 struct sf_ctx {
   int device = 0;
   hipStream_t stream = nullptr;
-  // shared KL basis (sf_set_basis)
+  // shared KL basis (sf_set_basis) or evaluation-only geometry
+  // (sf_set_piercepoints: D, r0, beta, d_pp / h_pp only)
   int D = 0;
+  int has_basis = 0;           // 1: d_c / d_pinv / d_u / d_eig belong to D
   double r0 = 100.0;
   double beta = 5.0 / 3.0;
   double* d_pp = nullptr;      // [D][3]
@@ -77,7 +79,7 @@ struct sf_ctx {
   // recorded after every launch that reads d_kdig / d_kflag: the next
   // prepass (on whatever stream) waits for it before rewriting them
   hipEvent_t kdig_read = nullptr;
-  double h_pp[3 * SF_MAX_DIR] = {};  // host copy of the piercepoints
+  double h_pp[3 * SF_MAX_EVAL_DIR] = {};  // host copy of the piercepoints
   // fit scratch
   uint8_t* d_skip = nullptr;   // [F][A] block skip flags
   size_t skip_cap = 0;
@@ -138,12 +140,15 @@ namespace sf {
 // screens from D = 45 (below, the fp64 MFMA share of the SIMD is small and
 // the LDS-staged kernels are store-bound already) on the fast epilogue with
 // float4-aligned output; SF_OPT_EVAL_INT = 0 and grids whose |Cpix| does not
-// fit the digits keep the fp64 contraction.
+// fit the digits keep the fp64 contraction, and so does the wide kernel
+// (D > 60, kl_eval_wide.hip).
+constexpr int kEvalMaxKS = 15;   // k-steps of the kl_eval_impl.h templates
+constexpr int kEvalWideMaxKS = SF_MAX_EVAL_DIR / 4;
 inline bool eval_int_applies(const sf_ctx* ctx, bool gain, unsigned flags,
                              bool out_aligned16) {
   return !gain && ctx->dig_ok && ctx->d_cdig && ctx->eval_int != 0 &&
          (flags & SF_EVAL_FAST_SINCOS) && ctx->n_pix % 4 == 0 && out_aligned16 &&
-         ctx->ksteps >= 12;
+         ctx->ksteps >= 12 && ctx->ksteps <= kEvalMaxKS;
 }
 
 struct RefSpec {
@@ -170,6 +175,10 @@ int pick_eval_kernel(const sf_ctx* ctx, bool gain, unsigned flags,
 int launch_eval(sf_ctx* ctx, const double* coef, const double* cxx,
                 const double* cyy, int64_t S, float* out, int64_t ring,
                 unsigned flags, unsigned* sums);
+// D > 60 (kEvalMaxKS < ksteps <= kEvalWideMaxKS): kl_eval_wide.hip
+int launch_eval_wide(sf_ctx* ctx, const double* coef, const double* cxx,
+                     const double* cyy, int64_t S, float* out, int64_t ring,
+                     unsigned flags, unsigned* sums);
 int launch_tess(sf_ctx* ctx, const int32_t* labels, int nx, int ny,
                 const double* phase, const double* amp_xx,
                 const double* amp_yy, int D, int64_t S, float* out,

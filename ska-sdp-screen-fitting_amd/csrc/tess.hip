@@ -34,6 +34,13 @@ __device__ __forceinline__ int reflect_idx(int i, int n) {
   return m < n ? m : 2 * n - 1 - m;
 }
 
+// Capacity of the per-slot value tables the kernels keep in LDS (D + 1
+// entries, the last the NaN row): 65 for D <= 64 -- the LDS footprint, and so
+// the occupancy, those kernels always had -- and 129 up to SF_MAX_EVAL_DIR.
+constexpr int kTabCap = 65;
+constexpr int kTabCapWide = SF_MAX_EVAL_DIR + 1;
+
+template <int TC>
 __global__ __launch_bounds__(256) void kl_tess_kernel(
     const int32_t* __restrict__ labels, int nx, int ny,
     const double* __restrict__ phase, const double* __restrict__ amp_xx,
@@ -42,7 +49,7 @@ __global__ __launch_bounds__(256) void kl_tess_kernel(
     int R, unsigned flags) {
 #pragma clang fp contract(off)
   __shared__ int lab[(kTT + 2 * kMaxR) * (kTT + 2 * kMaxR)];
-  __shared__ float table[65 * 4];  // + one NaN row for invalid labels
+  __shared__ float table[TC * 4];  // + one NaN row for invalid labels
   __shared__ float ybuf[4 * kTT * (kTT + 2 * kMaxR)];
   __shared__ double w[2 * kMaxR + 1];
   const int tiles_x = (nx + kTT - 1) / kTT;
@@ -247,7 +254,7 @@ __global__ __launch_bounds__(64 * NW) void kl_tess_gather_kernel(
 // Smoothed fill (0 < R <= kMaxR): wide tiles for long store runs.  A
 // workgroup (4 waves) owns a tile of kSmTH rows x kSmTW pixels (wave w:
 // rows w, w + 4, 4 pixels per lane, 1 KiB contiguous per (slot, plane)) and a
-// chunk of slots.  The tile's labels + halo sit in LDS as bytes (D <= 64,
+// chunk of slots.  The tile's labels + halo sit in LDS as bytes (D <= 128,
 // entry D = NaN for labels outside 1..D); per slot the raw value table
 // (kl_tess_table_kernel without scrub / swap, widened to double) goes to
 // LDS, the y pass writes the halo columns of the tile rows (fp64 sums in
@@ -265,8 +272,8 @@ constexpr int kSmSlots = 8;
 
 // RT > 0: the radius at compile time (taps unrolled, so the label and table
 // reads of a tap window go out together; LDS sized for RT: more resident
-// workgroups); RT = 0: any R <= kMaxR at run time.
-template <int RT, int NP>
+// workgroups); RT = 0: any R <= kMaxR at run time.  TC: table capacity.
+template <int RT, int NP, int TC = kTabCap>
 __global__ __launch_bounds__(256) void kl_tess_smooth_kernel(
     const int32_t* __restrict__ labels, int nx, int ny,
     const tess_v4f* __restrict__ tab, int D, int64_t S,
@@ -293,7 +300,7 @@ __global__ __launch_bounds__(256) void kl_tess_smooth_kernel(
   __shared__ unsigned char lab[(kSmTH + 2 * kR) * (kSmTW + 2 * kR)];
   // y-pass results: float, as scipy's float32 intermediate image
   __shared__ vyf_t ybuf[kSmTH * (kSmTW + 2 * kR)];
-  __shared__ vacc_t tbl[2][65];
+  __shared__ vacc_t tbl[2][TC];
   __shared__ double w[2 * kR + 1];
   const int DT = D + 1;
   const int W2 = kSmTW + 2 * R;  // halo tile width
@@ -453,7 +460,7 @@ constexpr int kBoxTH = 4;       // tile rows (one per wave)
 constexpr int kBoxSlots = 32;   // slots per work item (the tile setup amortises over them)
 constexpr int kBoxMaxR = 24;
 
-template <int RT, int NP>
+template <int RT, int NP, int TC = kTabCap>
 __global__ __launch_bounds__(256) void kl_tess_box_kernel(
     const int32_t* __restrict__ labels, int nx, int ny,
     const tess_v4f* __restrict__ tab, int D, int64_t S,
@@ -471,7 +478,7 @@ __global__ __launch_bounds__(256) void kl_tess_box_kernel(
   };
   constexpr int kR = RT > 0 ? RT : kBoxMaxR;  // LDS sizing
   constexpr int kW2 = kSmTW + 2 * kR;
-  constexpr unsigned char kMixed = 0xFF;       // D <= 64 < 0xFF
+  constexpr unsigned char kMixed = 0xFF;       // D <= 128 < 0xFF
   constexpr int kTapUnroll = RT > 0 ? RT : 4;
   const int R = RT > 0 ? RT : R_arg;
   const int W2 = kSmTW + 2 * R;
@@ -482,9 +489,9 @@ __global__ __launch_bounds__(256) void kl_tess_box_kernel(
   __shared__ unsigned short ylist[kBoxTH * kW2];  // mixed y windows
   __shared__ unsigned short xlist[kBoxTH * kSmTW];  // mixed (boundary) pixels
   __shared__ int n_list[2];
-  __shared__ vacc_t tbl[2][65];     // raw table entries, widened
-  __shared__ vyf_t yu[2][65];       // y pass of a uniform window, per entry
-  __shared__ tess_v4f xu[2][65];    // final value of a uniform box, per entry
+  __shared__ vacc_t tbl[2][TC];     // raw table entries, widened
+  __shared__ vyf_t yu[2][TC];       // y pass of a uniform window, per entry
+  __shared__ tess_v4f xu[2][TC];    // final value of a uniform box, per entry
   __shared__ vyf_t ybuf[kBoxTH * kW2];    // y pass of the mixed windows
   __shared__ tess_v4f xout[kBoxTH * kSmTW];  // final value of the mixed pixels
   __shared__ double w[2 * kR + 1];
@@ -746,9 +753,12 @@ int launch_tess(sf_ctx* ctx, const int32_t* labels, int nx, int ny,
   // sliding windows win: profiles/round3p_tess_box_sweep.txt)
   const bool box = R > 0 && R <= kBoxMaxR &&
                    (ctx->tess_box == 1 || (ctx->tess_box < 0 && amp_yy && R <= 5));
+  // D > 64: the kernels with the larger LDS tables
+  const bool wide = D + 1 > kTabCap;
   int chunk = box ? kBoxSlots : kSmSlots;
   if (R == 0) {
-    // the item's table slice in LDS: at most 64 KiB (63 slots at D = 64)
+    // the item's table slice in LDS: at most 64 KiB (63 slots at D = 64, 31
+    // at D = 128; D <= SF_MAX_EVAL_DIR keeps the clamped chunk >= 1)
     chunk = ctx->tess_slots > 0 ? ctx->tess_slots : kGatherSlotsAuto;
     if (chunk * DT * 16 > 65536) chunk = (int)(65536 / (DT * 16));
   }
@@ -772,16 +782,19 @@ int launch_tess(sf_ctx* ctx, const int32_t* labels, int nx, int ny,
       int64_t grid = n_tiles * n_sc;
       const int64_t cap = ((int64_t)1 << 31) / 256;
       if (grid > cap) grid = cap;  // workgroups walk the remaining items
+#define SF_BOX_T(RT, NP, TC)                                                        \
+  hipLaunchKernelGGL((kl_tess_box_kernel<RT, NP, TC>), dim3((unsigned)grid),        \
+                     dim3(256), 0, ctx->stream, labels, nx, ny, tab, D, Sb, out,    \
+                     ring, b % ring, d_w, R, n_tiles, n_sc, flags)
 #define SF_BOX(RT)                                                                  \
   do {                                                                              \
-    if (amp_yy)                                                                     \
-      hipLaunchKernelGGL((kl_tess_box_kernel<RT, 4>), dim3((unsigned)grid),         \
-                         dim3(256), 0, ctx->stream, labels, nx, ny, tab, D, Sb, out, \
-                         ring, b % ring, d_w, R, n_tiles, n_sc, flags);             \
-    else                                                                            \
-      hipLaunchKernelGGL((kl_tess_box_kernel<RT, 2>), dim3((unsigned)grid),         \
-                         dim3(256), 0, ctx->stream, labels, nx, ny, tab, D, Sb, out, \
-                         ring, b % ring, d_w, R, n_tiles, n_sc, flags);             \
+    if (wide) {                                                                     \
+      if (amp_yy) SF_BOX_T(RT, 4, kTabCapWide);                                     \
+      else SF_BOX_T(RT, 2, kTabCapWide);                                            \
+    } else {                                                                        \
+      if (amp_yy) SF_BOX_T(RT, 4, kTabCap);                                         \
+      else SF_BOX_T(RT, 2, kTabCap);                                                \
+    }                                                                               \
   } while (0)
       // compiled radii: sigma up to 2 px (R <= 8); wider ones run the
       // run-time radius variant
@@ -797,6 +810,7 @@ int launch_tess(sf_ctx* ctx, const int32_t* labels, int nx, int ny,
         default: SF_BOX(0);
       }
 #undef SF_BOX
+#undef SF_BOX_T
       SF_HIP(hipGetLastError());
       continue;
     }
@@ -821,6 +835,32 @@ int launch_tess(sf_ctx* ctx, const int32_t* labels, int nx, int ny,
   hipLaunchKernelGGL((kl_tess_smooth_kernel<RT, 2>), dim3((unsigned)grid), dim3(256), \
                      0, ctx->stream, labels, nx, ny, tab, D, Sb, out, ring, b % ring,  \
                      d_w, R, n_tiles, n_sc, flags)
+#define SF_SMOOTH_W(RT)                                                             \
+  do {                                                                              \
+    if (amp_yy)                                                                     \
+      hipLaunchKernelGGL((kl_tess_smooth_kernel<RT, 4, kTabCapWide>),               \
+                         dim3((unsigned)grid), dim3(256), 0, ctx->stream, labels,   \
+                         nx, ny, tab, D, Sb, out, ring, b % ring, d_w, R, n_tiles,  \
+                         n_sc, flags);                                              \
+    else                                                                            \
+      hipLaunchKernelGGL((kl_tess_smooth_kernel<RT, 2, kTabCapWide>),               \
+                         dim3((unsigned)grid), dim3(256), 0, ctx->stream, labels,   \
+                         nx, ny, tab, D, Sb, out, ring, b % ring, d_w, R, n_tiles,  \
+                         n_sc, flags);                                              \
+  } while (0)
+      // D > 64: the radii of sigma <= 2 px compiled, wider ones at run time
+      // (same bits)
+      if (wide) switch (R) {
+        case 1: SF_SMOOTH_W(1); break;
+        case 2: SF_SMOOTH_W(2); break;
+        case 3: SF_SMOOTH_W(3); break;
+        case 4: SF_SMOOTH_W(4); break;
+        case 5: SF_SMOOTH_W(5); break;
+        case 6: SF_SMOOTH_W(6); break;
+        case 7: SF_SMOOTH_W(7); break;
+        case 8: SF_SMOOTH_W(8); break;
+        default: SF_SMOOTH_W(0);
+      } else
       switch (R) {
         case 1: SF_SMOOTH(1); break;
         case 2: SF_SMOOTH(2); break;
@@ -853,6 +893,7 @@ int launch_tess(sf_ctx* ctx, const int32_t* labels, int nx, int ny,
       }
 #undef SF_SMOOTH
 #undef SF_SMOOTH2
+#undef SF_SMOOTH_W
       SF_HIP(hipGetLastError());
       continue;
     }
@@ -888,9 +929,14 @@ int launch_tess_tile(sf_ctx* ctx, const int32_t* labels, int nx, int ny,
                      int64_t ring, const double* d_w, int R, unsigned flags) {
   const int tiles = ((nx + kTT - 1) / kTT) * ((ny + kTT - 1) / kTT);
   const int64_t chunks = (S + kTessSlots - 1) / kTessSlots;
-  hipLaunchKernelGGL(kl_tess_kernel, dim3(tiles, (unsigned)chunks), dim3(256),
-                     0, ctx->stream, labels, nx, ny, phase, amp_xx, amp_yy, D,
-                     S, out, ring, d_w, R, flags);
+  if (D + 1 > kTabCap)
+    hipLaunchKernelGGL(kl_tess_kernel<kTabCapWide>, dim3(tiles, (unsigned)chunks),
+                       dim3(256), 0, ctx->stream, labels, nx, ny, phase, amp_xx,
+                       amp_yy, D, S, out, ring, d_w, R, flags);
+  else
+    hipLaunchKernelGGL(kl_tess_kernel<kTabCap>, dim3(tiles, (unsigned)chunks),
+                       dim3(256), 0, ctx->stream, labels, nx, ny, phase, amp_xx,
+                       amp_yy, D, S, out, ring, d_w, R, flags);
   SF_HIP(hipGetLastError());
   return SF_OK;
 }

@@ -21,7 +21,8 @@ SF_EVAL_NAN_SCRUB = 1
 SF_EVAL_FAST_SINCOS = 1 << 8
 SF_EVAL_NT_STORES = 1 << 9
 SF_EVAL_BIG_ENDIAN = 1 << 10
-SF_MAX_DIR = 60
+SF_MAX_DIR = 60        # directions per slot of set_basis / fit
+SF_MAX_EVAL_DIR = 128  # ... of set_piercepoints, set_grid, eval*, tess_fill
 SF_OPT_FIT_GENERAL = 1
 SF_OPT_EVAL_KERNEL = 2
 SF_OPT_EVAL_MAX_BLOCKS = 3
@@ -49,6 +50,7 @@ SF_EVAL_KERNEL_LDS8H = 5
 SF_EVAL_KERNEL_LDS16H = 6
 SF_EVAL_KERNEL_TILE3 = 7
 SF_EVAL_KERNEL_SHB = 8
+SF_EVAL_KERNEL_WIDE = 9
 EVAL_KERNEL_NAMES = {SF_EVAL_KERNEL_TILE: "kl_eval_kernel",
                      SF_EVAL_KERNEL_LDS4: "kl_eval_lds_kernel<4 waves>",
                      SF_EVAL_KERNEL_LDS8: "kl_eval_lds_kernel<8 waves>",
@@ -56,13 +58,14 @@ EVAL_KERNEL_NAMES = {SF_EVAL_KERNEL_TILE: "kl_eval_kernel",
                      SF_EVAL_KERNEL_LDS8H: "kl_eval_lds_kernel<8 waves, 2 tiles>",
                      SF_EVAL_KERNEL_LDS16H: "kl_eval_lds_kernel<16 waves, 2 tiles>",
                      SF_EVAL_KERNEL_TILE3: "kl_eval_kernel<3 waves/SIMD>",
-                     SF_EVAL_KERNEL_SHB: "kl_eval_kernel<Cpix in LDS>"}
+                     SF_EVAL_KERNEL_SHB: "kl_eval_kernel<Cpix in LDS>",
+                     SF_EVAL_KERNEL_WIDE: "kl_eval_wide_kernel"}
 
 # every symbol include/screenfit.h declares (checked by tests/test_capi.py)
 EXPORTED = (
     "sf_version", "sf_last_error", "sf_create", "sf_destroy", "sf_set_stream",
     "sf_synchronize", "sf_set_option", "sf_get_eval_kernel", "sf_get_eval_contraction", "sf_alloc", "sf_free", "sf_copy_h2d", "sf_copy_d2h",
-    "sf_set_basis", "sf_get_basis", "sf_kl_fit", "sf_get_fit_stats", "sf_get_fit_pool",
+    "sf_set_basis", "sf_set_piercepoints", "sf_get_basis", "sf_kl_fit", "sf_get_fit_stats", "sf_get_fit_pool",
     "sf_stream_create", "sf_stream_destroy", "sf_device_cus",
     "sf_set_grid", "sf_kl_eval", "sf_kl_eval_gain", "sf_kl_eval_sums",
     "sf_tess_fill", "sf_smooth",
@@ -133,6 +136,7 @@ def load_library(path=None):
             "sf_copy_h2d": ([vp, vp, vp, ctypes.c_size_t], c_int),
             "sf_copy_d2h": ([vp, vp, vp, ctypes.c_size_t], c_int),
             "sf_set_basis": ([vp, vp, c_int, c_dbl, c_dbl], c_int),
+            "sf_set_piercepoints": ([vp, vp, c_int, c_dbl, c_dbl], c_int),
             "sf_get_basis": ([vp, vp, vp, vp, vp], c_int),
             "sf_kl_fit": ([vp, vp, vp, c_int, c_int, c_int, ip,
                            ctypes.POINTER(FitParams), vp, vp, vp, vp], c_int),
@@ -262,6 +266,19 @@ class Context:
                                      float(r0), float(beta)), "sf_set_basis")
         self.D = pp.shape[0]
         self.grid = None
+
+    def set_piercepoints(self, pp, r0=100.0, beta=5.0 / 3.0):
+        """sf_set_piercepoints: the evaluation-only geometry (up to
+        SF_MAX_EVAL_DIR directions, no eigen-basis: ``set_grid`` and the
+        ``eval*`` calls work, ``fit`` and ``get_basis`` raise)."""
+        pp = np.ascontiguousarray(pp, dtype=np.float64)
+        assert pp.ndim == 2 and pp.shape[1] == 3
+        self.D = 0
+        self.grid = None
+        _check(self.lib.sf_set_piercepoints(self.h, pp.ctypes.data, pp.shape[0],
+                                            float(r0), float(beta)),
+               "sf_set_piercepoints")
+        self.D = pp.shape[0]
 
     def get_basis(self):
         D = self.D

@@ -17,7 +17,7 @@ import numpy as np
 from . import geometry
 from . import stationscreen
 from ._lib import (SF_EVAL_BIG_ENDIAN, SF_EVAL_FAST_SINCOS, SF_EVAL_NAN_SCRUB,
-                   SF_EVAL_NT_STORES, Context)
+                   SF_EVAL_NT_STORES, SF_MAX_DIR, Context)
 from .h5parm import H5parm, get_reference_station
 from .screen import Screen
 
@@ -54,7 +54,11 @@ class KLEvaluator:
         self.nx, self.ny = len(x_coord), len(y_coord)
         with torch.cuda.device(self.dev):
             self.ctx.set_stream(torch.cuda.current_stream(self.dev).cuda_stream)
-            self.ctx.set_basis(self.pp, r_0, beta)
+            if self.D > SF_MAX_DIR:
+                # evaluation needs no eigen-basis: up to SF_MAX_EVAL_DIR
+                self.ctx.set_piercepoints(self.pp, r_0, beta)
+            else:
+                self.ctx.set_basis(self.pp, r_0, beta)
             self.ctx.set_grid(x_coord, y_coord)
 
     def eval_device(self, coef_dev, out_dev=None, flags=DEFAULT_FLAGS):
