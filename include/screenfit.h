@@ -60,6 +60,9 @@ extern "C" {
 
 #define SF_MAX_DIR 60 /* directions per slot of sf_set_basis / sf_kl_fit (one
                          wavefront lane each; LDS-bound) */
+/* directions per slot of sf_set_basis_wide and of sf_kl_fit after it (above
+ * SF_MAX_DIR: one workgroup per slot, kl_fit_wide.hip) */
+#define SF_MAX_FIT_DIR 128
 /* directions per slot of the pixel side: sf_set_piercepoints, sf_set_grid,
  * sf_kl_eval / _gain / _sums and sf_tess_fill */
 #define SF_MAX_EVAL_DIR 128
@@ -259,6 +262,35 @@ int sf_copy_d2h(sf_ctx* ctx, void* dst_host, const void* src_dev, size_t bytes);
  */
 int sf_set_basis(sf_ctx* ctx, const double* pp_host, int D, double r0,
                  double beta);
+/*
+ * sf_set_basis for 1 <= D <= SF_MAX_FIT_DIR.  For D <= SF_MAX_DIR it IS
+ * sf_set_basis (basis, fit and evaluation bit for bit).  For 61..128
+ * directions it computes C, pinv(C) (absolute cutoff 1e-3), U (columns by
+ * descending |lambda|, ties by index) and the eigenvalues on the device with
+ * a workgroup Jacobi solver, binds the evaluation geometry exactly as
+ * sf_set_piercepoints does (sf_set_grid and sf_kl_eval* afterwards write the
+ * same bytes as after sf_set_piercepoints) and marks the context as holding
+ * a wide basis.  It synchronises and invalidates the pixel grid; a failed
+ * call leaves the context usable (no geometry, as after sf_create).
+ * On a wide-basis context:
+ *  - sf_get_basis returns the basis in the same layout;
+ *  - sf_kl_fit keeps its contract (screen types, niter, nsigma,
+ *    adjust_order, ref_ant / ant_offset / ref_phase, the block and
+ *    reference-station skips, NULL resid / w_out / order_out) on the wide
+ *    fit: one workgroup per slot, a slot with flagged directions decomposes
+ *    its own subset covariance (no mask cache).  The SF_OPT_FIT_* options are
+ *    ignored above SF_MAX_DIR directions.  The context keeps a workspace
+ *    for the matrices that do not fit the LDS: (3 - m) D (D | 1) doubles
+ *    per workgroup of the persistent grid, m = matrices that fit 160 KiB,
+ *    one workgroup per CU (64.5 MiB at D = 128 on 256 CUs, 19 MiB at D = 96,
+ *    13 MiB at D = 80, none for D <= 79),
+ *    freed by sf_destroy and by the next sf_set_basis* / sf_set_piercepoints;
+ *  - sf_get_fit_stats reports in n_masks the number of subset
+ *    decompositions the last fit ran, and n_general = 0;
+ *  - sf_get_fit_pool returns SF_EINVAL (its mask keys are 64-bit).
+ */
+int sf_set_basis_wide(sf_ctx* ctx, const double* pp_host, int D, double r0,
+                      double beta);
 /* Copy the device basis back (host [D][D] each; any pointer may be NULL).
  * SF_EINVAL on a context whose geometry came from sf_set_piercepoints. */
 int sf_get_basis(sf_ctx* ctx, double* c_host, double* pinv_c_host,
@@ -290,7 +322,8 @@ int sf_set_piercepoints(sf_ctx* ctx, const double* pp_host, int D, double r0,
  * coef): coef [T][F][A][D] float64 (the "phase_screen000" values),
  * resid [T][F][A][D] float64, w_out [T][F][A][D] float32 (weights after
  * outlier flagging), order_out [T][F][A] int32 (orders, the weights of the
- * "...resid" soltab).  Requires sf_set_basis with the same D
+ * "...resid" soltab).  Requires sf_set_basis (D <= SF_MAX_DIR) or
+ * sf_set_basis_wide (D <= SF_MAX_FIT_DIR) with the same D
  * (sf_set_piercepoints does not serve: SF_EINVAL).
  */
 int sf_kl_fit(sf_ctx* ctx, const double* phase, const float* weight, int T,
@@ -300,7 +333,8 @@ int sf_kl_fit(sf_ctx* ctx, const double* phase, const float* weight, int T,
 
 /* Statistics of the last sf_kl_fit (synchronises): number of distinct
  * flagged-direction masks whose subset basis was decomposed, and number of
- * slots that took the general (tiny-weight) path. */
+ * slots that took the general (tiny-weight) path.  (Wide-basis context:
+ * see sf_set_basis_wide.) */
 int sf_get_fit_stats(sf_ctx* ctx, int* n_masks, int* n_general);
 
 /* The subset bases the last sf_kl_fit decomposed (a test / inspection
@@ -312,7 +346,7 @@ int sf_get_fit_stats(sf_ctx* ctx, int* n_masks, int* n_general);
  * hold its eigenvalues (entries_host[i * (D*D + D)]); the rest of an entry
  * is unspecified.  Entries are in the order the
  * masks were numbered, which is not deterministic; *n_masks = how many
- * exist.  Synchronises. */
+ * exist.  Synchronises.  SF_EINVAL on a wide-basis context. */
 int sf_get_fit_pool(sf_ctx* ctx, uint64_t* masks_host, double* entries_host,
                     int max_masks, int* n_masks);
 

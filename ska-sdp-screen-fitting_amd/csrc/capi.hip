@@ -53,6 +53,19 @@ int dev_alloc(T** p, size_t count) {
   return SF_OK;
 }
 
+// A new geometry: the workspace and state buffers of the wide fit
+// (kl_fit_wide.hip) were sized for the previous D.
+void drop_wide(sf_ctx* ctx) {
+  ctx->wide = 0;
+  hipFree(ctx->d_wide_ws);
+  hipFree(ctx->d_wide_w);
+  hipFree(ctx->d_wide_o);
+  ctx->d_wide_ws = nullptr;
+  ctx->d_wide_w = nullptr;
+  ctx->d_wide_o = nullptr;
+  ctx->wide_ws_cap = ctx->wide_w_cap = ctx->wide_o_cap = 0;
+}
+
 #define SF_TRY(x)              \
   do {                         \
     int rc_ = (x);             \
@@ -90,6 +103,9 @@ int sf_destroy(sf_ctx* ctx) {
   hipFree(ctx->d_pinv);
   hipFree(ctx->d_u);
   hipFree(ctx->d_eig);
+  hipFree(ctx->d_wide_ws);
+  hipFree(ctx->d_wide_w);
+  hipFree(ctx->d_wide_o);
   hipFree(ctx->d_cfrag);
   hipFree(ctx->d_cdig);
   hipFree(ctx->d_kdig);
@@ -325,6 +341,7 @@ int sf_set_basis(sf_ctx* ctx, const double* pp, int D, double r0,
   // below must not leave a context whose D points at freed buffers
   ctx->D = 0;
   ctx->has_basis = 0;
+  drop_wide(ctx);
   ctx->nx = ctx->ny = 0;
   ctx->n_pix = 0;
   SF_TRY(dev_alloc(&ctx->d_pp, (size_t)3 * D));
@@ -361,6 +378,7 @@ int sf_set_piercepoints(sf_ctx* ctx, const double* pp, int D, double r0,
   // the eigen-basis buffers of an earlier sf_set_basis are not this D's
   ctx->D = 0;
   ctx->has_basis = 0;
+  drop_wide(ctx);
   ctx->nx = ctx->ny = 0;
   ctx->n_pix = 0;
   SF_TRY(dev_alloc(&ctx->d_pp, (size_t)3 * D));
@@ -371,6 +389,36 @@ int sf_set_piercepoints(sf_ctx* ctx, const double* pp, int D, double r0,
   ctx->r0 = r0;
   ctx->beta = beta;
   return SF_OK;
+}
+
+int sf_set_basis_wide(sf_ctx* ctx, const double* pp, int D, double r0,
+                      double beta) {
+  SF_REQUIRE(ctx && pp, SF_EINVAL, "sf_set_basis_wide: bad argument");
+  SF_REQUIRE(D >= 1 && D <= SF_MAX_FIT_DIR, SF_EINVAL,
+             "sf_set_basis_wide: D out of range [1, SF_MAX_FIT_DIR]");
+  // the lane-per-direction basis and fit serve: bit for bit sf_set_basis
+  if (D <= SF_MAX_DIR) return sf_set_basis(ctx, pp, D, r0, beta);
+  // the evaluation geometry exactly as sf_set_piercepoints binds it (it
+  // synchronises, invalidates the grid and drops the previous basis) ...
+  SF_TRY(sf_set_piercepoints(ctx, pp, D, r0, beta));
+  // ... then C, pinv(C), U and the eigenvalues; until they are complete the
+  // context has no geometry at all
+  ctx->D = 0;
+  SF_TRY(dev_alloc(&ctx->d_c, (size_t)D * D));
+  SF_TRY(dev_alloc(&ctx->d_pinv, (size_t)D * D));
+  SF_TRY(dev_alloc(&ctx->d_u, (size_t)D * D));
+  SF_TRY(dev_alloc(&ctx->d_eig, (size_t)SF_MAX_FIT_DIR));
+  SF_HIP(hipMemset(ctx->d_eig, 0, SF_MAX_FIT_DIR * sizeof(double)));
+  ctx->D = D;
+  int rc = sf::launch_basis_wide(ctx);
+  if (rc == SF_OK && hipStreamSynchronize(ctx->stream) != hipSuccess) {
+    set_error("sf_set_basis_wide: basis kernel failed");
+    rc = SF_EIO;
+  }
+  if (rc != SF_OK) ctx->D = 0;
+  ctx->has_basis = rc == SF_OK;
+  ctx->wide = rc == SF_OK;
+  return rc;
 }
 
 int sf_get_basis(sf_ctx* ctx, double* c, double* pinv, double* u,
@@ -456,6 +504,9 @@ int sf_get_fit_pool(sf_ctx* ctx, uint64_t* masks_host, double* entries_host,
   SF_REQUIRE(ctx && n_masks && max_masks >= 0, SF_EINVAL, "sf_get_fit_pool: bad argument");
   SF_REQUIRE(max_masks == 0 || (masks_host && entries_host), SF_EINVAL,
              "sf_get_fit_pool: NULL output");
+  SF_REQUIRE(!ctx->wide, SF_EINVAL,
+             "sf_get_fit_pool: no mask pool above SF_MAX_DIR directions "
+             "(sf_set_basis_wide: every flagged slot decomposes its own subset)");
   SF_HIP(hipSetDevice(ctx->device));
   SF_HIP(hipStreamSynchronize(ctx->stream));
   int c0 = 0;

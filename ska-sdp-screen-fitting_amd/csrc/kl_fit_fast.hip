@@ -1236,28 +1236,6 @@ __global__ __launch_bounds__(256) void kl_block_flag_kernel(
 // ---------------------------------------------------------------------------
 namespace {
 
-template <typename T>
-int grow(T** p, size_t& cap, size_t need, bool keep = false) {
-  if (*p && cap >= need) return SF_OK;
-  T* q = nullptr;
-  if (hipMalloc(reinterpret_cast<void**>(&q), need * sizeof(T)) != hipSuccess) {
-    set_error("hipMalloc failed (fit scratch)");
-    return SF_ENOMEM;
-  }
-  // callers synchronise the context stream before growing, so the old
-  // buffer is no longer written by queued kernels
-  if (keep && *p && cap > 0 &&
-      hipMemcpy(q, *p, cap * sizeof(T), hipMemcpyDeviceToDevice) != hipSuccess) {
-    (void)hipFree(q);
-    set_error("hipMemcpy failed (fit scratch grow)");
-    return SF_EIO;
-  }
-  if (*p) (void)hipFree(*p);
-  *p = q;
-  cap = need;
-  return SF_OK;
-}
-
 size_t next_pow2(size_t x) {
   size_t p = 1;
   while (p < x) p <<= 1;
@@ -1459,9 +1437,23 @@ static int launch_pass(sf_ctx* ctx, int it, const sf_fit_params* p,
                                          w_out, order_out);
 }
 
+int launch_block_sigma(sf_ctx* ctx, int T, int F, int A, const double* phase,
+                       const RefSpec& r, int screen_type, const double* resid,
+                       const float* w_out) {
+  hipLaunchKernelGGL(kl_block_sigma_kernel, dim3(F * A), dim3(256), 0,
+                     ctx->stream, T, F, A, ctx->D, phase, r.refph, r.sub,
+                     ctx->d_skip, r.skip, screen_type, resid, w_out,
+                     ctx->d_sigma);
+  SF_HIP(hipGetLastError());
+  return SF_OK;
+}
+
 int launch_fit(sf_ctx* ctx, const double* phase, const float* weight, int T,
                int F, int A, const sf_fit_params* p, double* coef,
                double* resid, float* w_out, int32_t* order_out) {
+  if (ctx->wide)
+    return launch_fit_wide(ctx, phase, weight, T, F, A, p, coef, resid, w_out,
+                           order_out);
   const int D = ctx->D;
   const int64_t S = (int64_t)T * F * A;
   const RefSpec r = ref_spec(p, A);
@@ -1563,11 +1555,8 @@ int launch_fit(sf_ctx* ctx, const double* phase, const float* weight, int T,
       SF_TRYF(launch_pass<true>(ctx, it, p, r, S, F, A, phase, coef, resid,
                                 w_out, order_out, false));
     if (block_flags && it + 1 < p->niter) {
-      hipLaunchKernelGGL(kl_block_sigma_kernel, dim3(F * A), dim3(256), 0,
-                         ctx->stream, T, F, A, D, phase, r.refph, r.sub,
-                         ctx->d_skip, r.skip, p->screen_type, resid, w_out,
-                         ctx->d_sigma);
-      SF_HIP(hipGetLastError());
+      SF_TRYF(launch_block_sigma(ctx, T, F, A, phase, r, p->screen_type, resid,
+                                 w_out));
       hipLaunchKernelGGL(kl_block_flag_kernel, dim3((unsigned)((S + 255) / 256)),
                          dim3(256), 0, ctx->stream, S, F, A, D, phase, r.refph,
                          r.sub, ctx->d_class, p->screen_type, p->nsigma,

@@ -30,6 +30,35 @@ void set_error(const std::string& msg);
     }                               \
   } while (0)
 
+#define SF_TRY_RC(x)               \
+  do {                             \
+    int rc_ = (x);                 \
+    if (rc_ != SF_OK) return rc_;  \
+  } while (0)
+
+// Device buffer of at least `need` elements (callers synchronise the
+// context's stream before growing, so queued kernels no longer write the old
+// buffer); keep = copy the old contents over.
+template <typename T>
+int grow(T** p, size_t& cap, size_t need, bool keep = false) {
+  if (*p && cap >= need) return SF_OK;
+  T* q = nullptr;
+  if (hipMalloc(reinterpret_cast<void**>(&q), need * sizeof(T)) != hipSuccess) {
+    set_error("hipMalloc failed (fit scratch)");
+    return SF_ENOMEM;
+  }
+  if (keep && *p && cap > 0 &&
+      hipMemcpy(q, *p, cap * sizeof(T), hipMemcpyDeviceToDevice) != hipSuccess) {
+    (void)hipFree(q);
+    set_error("hipMemcpy failed (fit scratch grow)");
+    return SF_EIO;
+  }
+  if (*p) (void)hipFree(*p);
+  *p = q;
+  cap = need;
+  return SF_OK;
+}
+
 // pixel tiling of the evaluation kernel (kl_eval.hip) -------------------------
 constexpr int kTiles = 4;                       // 16x16 MFMA tiles per wave, interleaved
 constexpr int kWavePix = 16 * kTiles;           // 64 consecutive pixels per wave
@@ -49,6 +78,8 @@ struct sf_ctx {
   // (sf_set_piercepoints: D, r0, beta, d_pp / h_pp only)
   int D = 0;
   int has_basis = 0;           // 1: d_c / d_pinv / d_u / d_eig belong to D
+  int wide = 0;                // 1: the basis came from sf_set_basis_wide with
+                               // D > SF_MAX_DIR (kl_fit_wide.hip fits it)
   double r0 = 100.0;
   double beta = 5.0 / 3.0;
   double* d_pp = nullptr;      // [D][3]
@@ -56,6 +87,14 @@ struct sf_ctx {
   double* d_pinv = nullptr;    // [D][D]
   double* d_u = nullptr;       // [D][D] (columns sorted by |lambda| desc)
   double* d_eig = nullptr;     // [D]    (signed eigenvalues, sorted)
+  // wide fit (kl_fit_wide.hip): the matrices of the basis kernel, then of the
+  // fit workgroups that do not fit the LDS; state when the caller passes NULL
+  double* d_wide_ws = nullptr;
+  size_t wide_ws_cap = 0;      // doubles
+  float* d_wide_w = nullptr;
+  size_t wide_w_cap = 0;
+  int32_t* d_wide_o = nullptr;
+  size_t wide_o_cap = 0;
   // pixel grid (sf_set_grid)
   int nx = 0, ny = 0;
   int64_t n_pix = 0;
@@ -165,6 +204,16 @@ int launch_fit_general(sf_ctx* ctx, const int* slot_list, const int* n_list,
                        const sf_fit_params* p, const RefSpec& r, double* coef,
                        double* resid, float* w_out, int32_t* order_out);
 int launch_basis(sf_ctx* ctx);
+// tec / amplitude outlier sigma per (station, freq) block into ctx->d_sigma
+// (kl_block_sigma_kernel, kl_fit_fast.hip; any D)
+int launch_block_sigma(sf_ctx* ctx, int T, int F, int A, const double* phase,
+                       const RefSpec& r, int screen_type, const double* resid,
+                       const float* w_out);
+// 60 < D <= SF_MAX_FIT_DIR: kl_fit_wide.hip
+int launch_basis_wide(sf_ctx* ctx);
+int launch_fit_wide(sf_ctx* ctx, const double* phase, const float* weight,
+                    int T, int F, int A, const sf_fit_params* p, double* coef,
+                    double* resid, float* w_out, int32_t* order_out);
 int launch_cpix(sf_ctx* ctx, const double* d_x, const double* d_y);
 int launch_cdig(sf_ctx* ctx, const double* d_x, const double* d_y, int* d_bad);
 int launch_fit(sf_ctx* ctx, const double* phase, const float* weight, int T,

@@ -22,6 +22,7 @@ SF_EVAL_FAST_SINCOS = 1 << 8
 SF_EVAL_NT_STORES = 1 << 9
 SF_EVAL_BIG_ENDIAN = 1 << 10
 SF_MAX_DIR = 60        # directions per slot of set_basis / fit
+SF_MAX_FIT_DIR = 128   # ... of set_basis_wide / fit after it
 SF_MAX_EVAL_DIR = 128  # ... of set_piercepoints, set_grid, eval*, tess_fill
 SF_OPT_FIT_GENERAL = 1
 SF_OPT_EVAL_KERNEL = 2
@@ -65,7 +66,7 @@ EVAL_KERNEL_NAMES = {SF_EVAL_KERNEL_TILE: "kl_eval_kernel",
 EXPORTED = (
     "sf_version", "sf_last_error", "sf_create", "sf_destroy", "sf_set_stream",
     "sf_synchronize", "sf_set_option", "sf_get_eval_kernel", "sf_get_eval_contraction", "sf_alloc", "sf_free", "sf_copy_h2d", "sf_copy_d2h",
-    "sf_set_basis", "sf_set_piercepoints", "sf_get_basis", "sf_kl_fit", "sf_get_fit_stats", "sf_get_fit_pool",
+    "sf_set_basis", "sf_set_basis_wide", "sf_set_piercepoints", "sf_get_basis", "sf_kl_fit", "sf_get_fit_stats", "sf_get_fit_pool",
     "sf_stream_create", "sf_stream_destroy", "sf_device_cus",
     "sf_set_grid", "sf_kl_eval", "sf_kl_eval_gain", "sf_kl_eval_sums",
     "sf_tess_fill", "sf_smooth",
@@ -136,6 +137,7 @@ def load_library(path=None):
             "sf_copy_h2d": ([vp, vp, vp, ctypes.c_size_t], c_int),
             "sf_copy_d2h": ([vp, vp, vp, ctypes.c_size_t], c_int),
             "sf_set_basis": ([vp, vp, c_int, c_dbl, c_dbl], c_int),
+            "sf_set_basis_wide": ([vp, vp, c_int, c_dbl, c_dbl], c_int),
             "sf_set_piercepoints": ([vp, vp, c_int, c_dbl, c_dbl], c_int),
             "sf_get_basis": ([vp, vp, vp, vp, vp], c_int),
             "sf_kl_fit": ([vp, vp, vp, c_int, c_int, c_int, ip,
@@ -266,6 +268,19 @@ class Context:
                                      float(r0), float(beta)), "sf_set_basis")
         self.D = pp.shape[0]
         self.grid = None
+
+    def set_basis_wide(self, pp, r0=100.0, beta=5.0 / 3.0):
+        """sf_set_basis_wide: the basis for up to SF_MAX_FIT_DIR directions
+        (``set_basis`` itself up to SF_MAX_DIR; above, the workgroup-per-slot
+        fit and the wide evaluation serve; ``fit_pool`` raises there)."""
+        pp = np.ascontiguousarray(pp, dtype=np.float64)
+        assert pp.ndim == 2 and pp.shape[1] == 3
+        self.D = 0
+        self.grid = None
+        _check(self.lib.sf_set_basis_wide(self.h, pp.ctypes.data, pp.shape[0],
+                                          float(r0), float(beta)),
+               "sf_set_basis_wide")
+        self.D = pp.shape[0]
 
     def set_piercepoints(self, pp, r0=100.0, beta=5.0 / 3.0):
         """sf_set_piercepoints: the evaluation-only geometry (up to

@@ -105,6 +105,14 @@ def setup_shard(local, ant_offset, n_ant_total, rad, dec, width_deg,
                 ref_phase=refph, ant_offset=ant_offset)
 
 
+def bind_shard_basis(ctx, setup, r_0=100.0, beta=5.0 / 3.0):
+    """Bind the shared KL basis of ``setup_shard``'s piercepoints on this
+    rank's context, for the fit and the evaluation alike: ``set_basis_wide``
+    is ``set_basis`` up to SF_MAX_DIR directions and the wide basis (fit by
+    csrc/kl_fit_wide.hip, wide evaluation kernel) up to SF_MAX_FIT_DIR."""
+    ctx.set_basis_wide(setup["piercepoints"], r_0, beta)
+
+
 def device_identity(torch, device):
     """Which physical GPU a rank runs on: its torch index, PCI address and
     UUID (what ``rocm-smi`` / the kernel name the card by)."""

@@ -8,7 +8,9 @@ of csrc/kl_fit_fast.hip (one slot per wavefront, two per wavefront in 32-lane
 groups for D <= 32; eigenbasis solve), with ``kl_fit_general_kernel``
 (csrc/kl_fit.hip) for slots whose weights sit at the pinv cutoff.  The host does
 only the O(A + D) setup: piercepoints and midpoint, per-station orders, the
-shared basis upload, and the soltab bookkeeping.
+shared basis upload, and the soltab bookkeeping.  With 61 to 128 directions
+(SF_MAX_FIT_DIR) the basis is bound through ``sf_set_basis_wide`` and the fit
+runs one workgroup per slot (csrc/kl_fit_wide.hip).
 """
 
 import logging
@@ -16,7 +18,7 @@ import logging
 import numpy as np
 
 from . import geometry
-from ._lib import (SF_MAX_DIR, SF_MAX_EVAL_DIR, SF_SCREEN_AMPLITUDE,
+from ._lib import (SF_MAX_DIR, SF_MAX_FIT_DIR, SF_SCREEN_AMPLITUDE,
                    SF_SCREEN_PHASE, SF_SCREEN_TEC, ScreenFitError,
                    private_context)
 
@@ -45,23 +47,23 @@ def station_orders(station_positions, ref_ant, order, min_order=5,
 def _device_fit(phase, weight, pp, st_order, screen_type, niter, nsigma,
                 adjust_order, ref_ant, beta, r_0, device=0):
     """Run sf_kl_fit on host arrays [T, F, A, D]; returns host arrays."""
+    T, F, A, D = phase.shape
+    if D > SF_MAX_FIT_DIR:
+        raise ScreenFitError(
+            f"the fit is limited to SF_MAX_FIT_DIR = {SF_MAX_FIT_DIR} "
+            f"directions ({D} given)")
     import torch
 
-    T, F, A, D = phase.shape
     dev = torch.device("cuda", device)
     # a context of its own for the basis + fit sequence: another thread's
     # fit or screen cannot re-base it between the two
     with private_context(device) as ctx, torch.cuda.device(dev):
         ctx.set_stream(torch.cuda.current_stream(dev).cuda_stream)
-        try:
+        if D > SF_MAX_DIR:
+            # 61..128 directions: the workgroup-per-slot fit (kl_fit_wide.hip)
+            ctx.set_basis_wide(pp, r_0, beta)
+        else:
             ctx.set_basis(pp, r_0, beta)
-        except ScreenFitError as exc:
-            if D > SF_MAX_DIR:
-                raise ScreenFitError(
-                    f"{exc}: the fit is limited to SF_MAX_DIR = {SF_MAX_DIR} "
-                    f"directions ({D} given); only the evaluation of fitted "
-                    f"screens goes to SF_MAX_EVAL_DIR = {SF_MAX_EVAL_DIR}") from exc
-            raise
         ph = torch.from_numpy(np.ascontiguousarray(phase, np.float64)).to(dev)
         wt = torch.from_numpy(np.ascontiguousarray(weight, np.float32)).to(dev)
         coef = torch.empty_like(ph)
