@@ -21,6 +21,10 @@
  *   sf_kl_eval    <- KLScreen.make_matrix + calculate_kl_screen + the NaN
  *                    scrub of Screen.write (kl_screen.py:192-449,
  *                    screen.py:343-378)
+ *   sf_set_points / sf_kl_eval_points / sf_kl_eval_point_values <-
+ *                    calculate_kl_screen at a list of positions instead of
+ *                    every pixel (kl_screen.py:411-449) and the Jones terms
+ *                    make_matrix forms from it (kl_screen.py:319-378)
  *
  * Conventions
  *  - Plain C types only.  Return 0 on success, a negative errno-style code
@@ -392,6 +396,31 @@ int sf_kl_eval_sums(sf_ctx* ctx, const double* coef_phase,
                     const double* coef_xx, const double* coef_yy, int64_t S,
                     float* out, int64_t ring, unsigned flags,
                     uint32_t* slot_sums);
+
+/*
+ * Screens sampled at positions (kl_points.hip): the value
+ * calculate_kl_screen (kl_screen.py:411-449) gives at each of P positions,
+ * without a pixel grid or a cube.  The point basis Cpix[p][d] =
+ * -(|pp_d - (x_p, y_p, 0)|^2 / r0^2)^(beta/2) / 2 is sf_set_grid's expression:
+ * a point at (X[i], Y[j]) evaluates as pixel (y=j, x=i) of that grid.
+ */
+#define SF_MAX_POINTS 4096
+/* P screen positions (host [P][2] float64: x, y in piercepoint coordinates).
+ * Needs the geometry of sf_set_basis / sf_set_basis_wide / sf_set_piercepoints
+ * (else SF_EINVAL); the next of those calls drops the points, as it drops the
+ * grid.  Independent of sf_set_grid: both may be bound at once.  Synchronises. */
+int sf_set_points(sf_ctx* ctx, const double* xy_host, int P);
+/* Jones planes at the bound points (kl_screen.py:319-378 at positions):
+ * device out [S][4][P] float32, planes as sf_kl_eval.  coef_xx and coef_yy
+ * both NULL (phase screens) or both given (gain; as sf_kl_eval_gain).  Device
+ * coef arrays [S][D] float64; the output needs 4-byte alignment only.  flags:
+ * SF_EVAL_NAN_SCRUB, SF_EVAL_FAST_SINCOS; any other bit is SF_EINVAL. */
+int sf_kl_eval_points(sf_ctx* ctx, const double* coef_phase, const double* coef_xx,
+                      const double* coef_yy, int64_t S, float* planes, unsigned flags);
+/* Screen values sum_d Cpix[p][d] coef[s][d] (kl_screen.py:411-449; rad, TECU
+ * or log10 amplitude, whatever was fitted; NaN coefficients give NaN): device
+ * out [S][P] float64. */
+int sf_kl_eval_point_values(sf_ctx* ctx, const double* coef, int64_t S, double* values);
 
 /*
  * Tessellated (Voronoi) screens: fill every pixel with the values of the

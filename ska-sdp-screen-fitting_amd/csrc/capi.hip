@@ -107,6 +107,8 @@ int sf_destroy(sf_ctx* ctx) {
   hipFree(ctx->d_wide_w);
   hipFree(ctx->d_wide_o);
   hipFree(ctx->d_cfrag);
+  hipFree(ctx->d_pxy);
+  hipFree(ctx->d_pfrag);
   hipFree(ctx->d_cdig);
   hipFree(ctx->d_kdig);
   hipFree(ctx->d_kflag);
@@ -344,6 +346,7 @@ int sf_set_basis(sf_ctx* ctx, const double* pp, int D, double r0,
   drop_wide(ctx);
   ctx->nx = ctx->ny = 0;
   ctx->n_pix = 0;
+  ctx->n_points = 0;
   SF_TRY(dev_alloc(&ctx->d_pp, (size_t)3 * D));
   SF_TRY(dev_alloc(&ctx->d_c, (size_t)D * D));
   SF_TRY(dev_alloc(&ctx->d_pinv, (size_t)D * D));
@@ -381,6 +384,7 @@ int sf_set_piercepoints(sf_ctx* ctx, const double* pp, int D, double r0,
   drop_wide(ctx);
   ctx->nx = ctx->ny = 0;
   ctx->n_pix = 0;
+  ctx->n_points = 0;
   SF_TRY(dev_alloc(&ctx->d_pp, (size_t)3 * D));
   SF_HIP(hipMemcpy(ctx->d_pp, pp, sizeof(double) * 3 * D,
                    hipMemcpyHostToDevice));
@@ -665,6 +669,65 @@ int sf_kl_eval_sums(sf_ctx* ctx, const double* coef_phase,
   SF_HIP(hipSetDevice(ctx->device));
   return sf::launch_eval(ctx, coef_phase, coef_xx, coef_yy, S, out, ring, flags,
                          reinterpret_cast<unsigned*>(slot_sums));
+}
+
+int sf_set_points(sf_ctx* ctx, const double* xy, int P) {
+  SF_REQUIRE(ctx, SF_EINVAL, "sf_set_points: NULL context");
+  SF_REQUIRE(ctx->D > 0, SF_EINVAL,
+             "sf_set_points: call sf_set_basis, sf_set_basis_wide or "
+             "sf_set_piercepoints first");
+  SF_REQUIRE(xy, SF_EINVAL, "sf_set_points: NULL positions");
+  SF_REQUIRE(P >= 1 && P <= SF_MAX_POINTS, SF_EINVAL,
+             "sf_set_points: P out of range [1, SF_MAX_POINTS]");
+  for (int i = 0; i < 2 * P; ++i)
+    SF_REQUIRE(std::isfinite(xy[i]), SF_EINVAL, "sf_set_points: non-finite coordinate");
+  SF_HIP(hipSetDevice(ctx->device));
+  // queued evaluations may still read the previous point basis
+  SF_HIP(hipStreamSynchronize(ctx->stream));
+  ctx->n_points = 0;  // no usable points until the basis is built
+  if (ctx->pt_cus == 0) SF_TRY(sf_device_cus(ctx, &ctx->pt_cus));
+  const int tiles = sf::points_tiles(P), ks_pad = sf::points_ks_pad(ctx->D);
+  SF_TRY(dev_alloc(&ctx->d_pxy, (size_t)2 * P));
+  SF_TRY(dev_alloc(&ctx->d_pfrag, (size_t)tiles * ks_pad * 64));
+  SF_HIP(hipMemcpy(ctx->d_pxy, xy, sizeof(double) * 2 * P, hipMemcpyHostToDevice));
+  ctx->pt_tiles = tiles;
+  ctx->pt_ks_pad = ks_pad;
+  ctx->n_points = P;
+  int rc = sf::launch_points_cpix(ctx);
+  if (rc == SF_OK && hipStreamSynchronize(ctx->stream) != hipSuccess) {
+    set_error("sf_set_points: point basis kernel failed");
+    rc = SF_EIO;
+  }
+  if (rc != SF_OK) ctx->n_points = 0;
+  return rc;
+}
+
+int sf_kl_eval_points(sf_ctx* ctx, const double* coef_phase, const double* coef_xx,
+                      const double* coef_yy, int64_t S, float* planes,
+                      unsigned flags) {
+  SF_REQUIRE(ctx, SF_EINVAL, "sf_kl_eval_points: NULL context");
+  SF_REQUIRE(ctx->D > 0 && ctx->n_points > 0 && ctx->d_pfrag, SF_EINVAL,
+             "sf_kl_eval_points: call sf_set_points first");
+  SF_REQUIRE(coef_phase && planes, SF_EINVAL, "sf_kl_eval_points: NULL argument");
+  SF_REQUIRE((coef_xx == nullptr) == (coef_yy == nullptr), SF_EINVAL,
+             "sf_kl_eval_points: give both amplitude coefficient sets or neither");
+  SF_REQUIRE(S >= 1, SF_EINVAL, "sf_kl_eval_points: S must be >= 1");
+  SF_REQUIRE((flags & ~(SF_EVAL_NAN_SCRUB | SF_EVAL_FAST_SINCOS)) == 0, SF_EINVAL,
+             "sf_kl_eval_points: flags other than SF_EVAL_NAN_SCRUB and "
+             "SF_EVAL_FAST_SINCOS");
+  SF_HIP(hipSetDevice(ctx->device));
+  return sf::launch_eval_points(ctx, coef_phase, coef_xx, coef_yy, S, planes, flags);
+}
+
+int sf_kl_eval_point_values(sf_ctx* ctx, const double* coef, int64_t S,
+                            double* values) {
+  SF_REQUIRE(ctx, SF_EINVAL, "sf_kl_eval_point_values: NULL context");
+  SF_REQUIRE(ctx->D > 0 && ctx->n_points > 0 && ctx->d_pfrag, SF_EINVAL,
+             "sf_kl_eval_point_values: call sf_set_points first");
+  SF_REQUIRE(coef && values, SF_EINVAL, "sf_kl_eval_point_values: NULL argument");
+  SF_REQUIRE(S >= 1, SF_EINVAL, "sf_kl_eval_point_values: S must be >= 1");
+  SF_HIP(hipSetDevice(ctx->device));
+  return sf::launch_eval_point_values(ctx, coef, S, values);
 }
 
 // scipy.ndimage._gaussian_kernel1d(sigma, 0, int(4 sigma + 0.5)) uploaded to

@@ -119,6 +119,13 @@ struct sf_ctx {
   // prepass (on whatever stream) waits for it before rewriting them
   hipEvent_t kdig_read = nullptr;
   double h_pp[3 * SF_MAX_EVAL_DIR] = {};  // host copy of the piercepoints
+  // screen positions (sf_set_points, kl_points.hip)
+  int n_points = 0;            // 0: none bound
+  int pt_tiles = 0;            // 16-point tiles, padded to whole passes
+  int pt_ks_pad = 0;           // k-steps, padded to the k-loop's trip
+  int pt_cus = 0;              // compute units of the device
+  double* d_pxy = nullptr;     // [P][2]
+  double* d_pfrag = nullptr;   // [pt_tiles][pt_ks_pad][64] MFMA B fragments
   // fit scratch
   uint8_t* d_skip = nullptr;   // [F][A] block skip flags
   size_t skip_cap = 0;
@@ -228,6 +235,15 @@ int launch_eval(sf_ctx* ctx, const double* coef, const double* cxx,
 int launch_eval_wide(sf_ctx* ctx, const double* coef, const double* cxx,
                      const double* cyy, int64_t S, float* out, int64_t ring,
                      unsigned flags, unsigned* sums);
+// screen positions (kl_points.hip): padded shapes of the point basis, its
+// kernel (d_pxy -> d_pfrag) and the slot-major evaluation at the points
+int points_ks_pad(int D);
+int points_tiles(int P);
+int launch_points_cpix(sf_ctx* ctx);
+int launch_eval_points(sf_ctx* ctx, const double* coef, const double* cxx,
+                       const double* cyy, int64_t S, float* planes, unsigned flags);
+int launch_eval_point_values(sf_ctx* ctx, const double* coef, int64_t S,
+                             double* values);
 int launch_tess(sf_ctx* ctx, const int32_t* labels, int nx, int ny,
                 const double* phase, const double* amp_xx,
                 const double* amp_yy, int D, int64_t S, float* out,

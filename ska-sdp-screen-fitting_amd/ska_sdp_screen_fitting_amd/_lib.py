@@ -24,6 +24,7 @@ SF_EVAL_BIG_ENDIAN = 1 << 10
 SF_MAX_DIR = 60        # directions per slot of set_basis / fit
 SF_MAX_FIT_DIR = 128   # ... of set_basis_wide / fit after it
 SF_MAX_EVAL_DIR = 128  # ... of set_piercepoints, set_grid, eval*, tess_fill
+SF_MAX_POINTS = 4096   # positions of set_points
 SF_OPT_FIT_GENERAL = 1
 SF_OPT_EVAL_KERNEL = 2
 SF_OPT_EVAL_MAX_BLOCKS = 3
@@ -70,6 +71,7 @@ EXPORTED = (
     "sf_stream_create", "sf_stream_destroy", "sf_device_cus",
     "sf_set_grid", "sf_kl_eval", "sf_kl_eval_gain", "sf_kl_eval_sums",
     "sf_tess_fill", "sf_smooth",
+    "sf_set_points", "sf_kl_eval_points", "sf_kl_eval_point_values",
 )
 
 
@@ -157,6 +159,9 @@ def load_library(path=None):
             "sf_tess_fill": ([vp, vp, c_int, c_int, vp, vp, vp, c_int, i64, vp,
                               i64, c_dbl, ctypes.c_uint], c_int),
             "sf_smooth": ([vp, vp, c_int, c_int, i64, c_dbl, ctypes.c_uint], c_int),
+            "sf_set_points": ([vp, vp, c_int], c_int),
+            "sf_kl_eval_points": ([vp, vp, vp, vp, i64, vp, ctypes.c_uint], c_int),
+            "sf_kl_eval_point_values": ([vp, vp, i64, vp], c_int),
         }
         for name, (args, res) in sig.items():
             fn = getattr(lib, name)
@@ -212,6 +217,7 @@ class Context:
         self.h = h
         self.D = 0
         self.grid = None
+        self.points = 0  # positions bound by set_points
         self.options = {}  # sf_set_option values set through this object
 
     def close(self):
@@ -268,6 +274,7 @@ class Context:
                                      float(r0), float(beta)), "sf_set_basis")
         self.D = pp.shape[0]
         self.grid = None
+        self.points = 0
 
     def set_basis_wide(self, pp, r0=100.0, beta=5.0 / 3.0):
         """sf_set_basis_wide: the basis for up to SF_MAX_FIT_DIR directions
@@ -277,6 +284,7 @@ class Context:
         assert pp.ndim == 2 and pp.shape[1] == 3
         self.D = 0
         self.grid = None
+        self.points = 0  # positions bound by set_points
         _check(self.lib.sf_set_basis_wide(self.h, pp.ctypes.data, pp.shape[0],
                                           float(r0), float(beta)),
                "sf_set_basis_wide")
@@ -290,6 +298,7 @@ class Context:
         assert pp.ndim == 2 and pp.shape[1] == 3
         self.D = 0
         self.grid = None
+        self.points = 0  # positions bound by set_points
         _check(self.lib.sf_set_piercepoints(self.h, pp.ctypes.data, pp.shape[0],
                                             float(r0), float(beta)),
                "sf_set_piercepoints")
@@ -376,6 +385,38 @@ class Context:
             self._dev(out, np.float32, self._out_numel(S, ring), "out"), ring,
             int(flags)), "sf_kl_eval")
 
+
+    def set_points(self, xy):
+        """sf_set_points: P screen positions ``xy`` [P, 2] (x, y in
+        piercepoint coordinates) for ``eval_points`` / ``eval_point_values``;
+        the next ``set_basis*`` / ``set_piercepoints`` drops them."""
+        xy = np.ascontiguousarray(xy, dtype=np.float64)
+        if xy.ndim != 2 or xy.shape[1] != 2:
+            raise ValueError(f"xy: shape {xy.shape}, expected (P, 2)")
+        self.points = 0
+        _check(self.lib.sf_set_points(self.h, xy.ctypes.data, xy.shape[0]),
+               "sf_set_points")
+        self.points = xy.shape[0]
+
+    def eval_points(self, coef, S, planes, coef_xx=None, coef_yy=None,
+                    flags=SF_EVAL_NAN_SCRUB | SF_EVAL_FAST_SINCOS):
+        """sf_kl_eval_points: Jones planes [S, 4, P] float32 at the bound
+        points (gain planes with ``coef_xx`` / ``coef_yy``)."""
+        n = int(S) * self.D
+        _check(self.lib.sf_kl_eval_points(
+            self.h, self._dev(coef, np.float64, n, "coef"),
+            self._dev(coef_xx, np.float64, n, "coef_xx"),
+            self._dev(coef_yy, np.float64, n, "coef_yy"), int(S),
+            self._dev(planes, np.float32, int(S) * 4 * self.points, "planes"),
+            int(flags)), "sf_kl_eval_points")
+
+    def eval_point_values(self, coef, S, values):
+        """sf_kl_eval_point_values: the screen values [S, P] float64 at the
+        bound points, in the coefficients' own units."""
+        _check(self.lib.sf_kl_eval_point_values(
+            self.h, self._dev(coef, np.float64, int(S) * self.D, "coef"), int(S),
+            self._dev(values, np.float64, int(S) * self.points, "values")),
+            "sf_kl_eval_point_values")
 
     def device_cus(self):
         n = ctypes.c_int(0)

@@ -11,7 +11,11 @@ they are O(D + N) host computations that set up the device work:
   (kl_screen.py:238-261): image TAN WCS (CRPIX N/2, CDELT -/+cell), pixel ->
   world for the diagonal pixels (i, i) only (Q8), then the piercepoint TAN;
 * ``sin_world2pix`` <- the RA---SIN / DEC--SIN axes of the FITS cube
-  (processing_utils.py:232-246), used to locate patch pixels.
+  (processing_utils.py:232-246), used to locate patch pixels;
+* ``screen_xy``     <- the second pass of ``piercepoints``: a sky position in
+  the screen's (piercepoint) coordinates;
+* ``patch_pixels``  <- the pixel lookup of the reference's acceptance test
+  (tests/test_fit_screens.py): ``int(np.round(.))`` of the cube's SIN WCS.
 
 Formulas are the standard closed forms (Calabretta & Greisen 2002) with the
 native longitude of the celestial pole at 180 deg; PV2_1 has no effect on TAN.
@@ -59,9 +63,14 @@ _PP_CRPIX = (1000.0, 1000.0)
 _PP_CDELT = (-0.0005, 0.0005)
 
 
-def _pp_xy(ra_deg, dec_deg, ref_ra, ref_dec):
-    return tan_world2pix(ra_deg, dec_deg, (float(ref_ra), float(ref_dec)),
+def screen_xy(ra_deg, dec_deg, mid_ra, mid_dec):
+    """Screen coordinates (x, y) of sky positions: the TAN projection about
+    the screen's midpoint that ``piercepoints`` applies to the directions."""
+    return tan_world2pix(ra_deg, dec_deg, (float(mid_ra), float(mid_dec)),
                          _PP_CRPIX, _PP_CDELT)
+
+
+_pp_xy = screen_xy
 
 
 def midpoint(ra_deg, dec_deg):
@@ -109,3 +118,20 @@ def grid_coords(rad, dec, width_deg, cellsize_deg, mid_ra, mid_dec):
                            (-cellsize_deg, cellsize_deg))
     x, y = _pp_xy(ra, de, mid_ra, mid_dec)
     return np.asarray(x), np.asarray(y)
+
+
+def patch_pixels(ra_deg, dec_deg, rad, dec, width_deg, cellsize_deg):
+    """Pixel (ix, iy) of the a-term image that holds each sky position, as
+    the reference's acceptance test looks patches up: ``int(np.round(.))`` of
+    the FITS header's SIN WCS (CRPIX = N / 2, CDELT = -/+cell; Q8 makes the
+    cube entry ``[..., iy, ix]``), and a mask of the positions inside the
+    N x N image."""
+    n = grid_size(width_deg, cellsize_deg)
+    px, py = sin_world2pix(ra_deg, dec_deg, (rad, dec), (n / 2.0, n / 2.0),
+                           (-cellsize_deg, cellsize_deg))
+    px, py = np.atleast_1d(px), np.atleast_1d(py)
+    ok = np.isfinite(px) & np.isfinite(py)
+    ix = np.where(ok, np.round(px), -1).astype(np.int64)
+    iy = np.where(ok, np.round(py), -1).astype(np.int64)
+    inside = ok & (ix >= 0) & (ix < n) & (iy >= 0) & (iy < n)
+    return ix, iy, inside

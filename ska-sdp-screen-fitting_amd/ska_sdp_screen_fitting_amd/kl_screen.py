@@ -7,7 +7,10 @@ subset-eigenbasis and classify kernels of csrc/kl_fit_fast.hip);
 ``make_matrix`` and ``write`` evaluate the screens with ``sf_kl_eval`` (the
 LDS-staged ``kl_eval_lds_kernel`` or the register-tile ``kl_eval_kernel`` of
 csrc/kl_eval.hip, chosen per D: an MFMA float64 contraction + sincos
-epilogue) instead of a per-pixel Python loop in a process pool.
+epilogue) instead of a per-pixel Python loop in a process pool.  ``sample``
+and ``patch_errors`` evaluate them at sky positions only
+(``sf_kl_eval_points``, csrc/kl_points.hip): what the cube holds at the
+calibrator patches -- the reference's acceptance quantity -- without the cube.
 """
 
 import multiprocessing
@@ -17,7 +20,7 @@ import numpy as np
 from . import geometry
 from . import stationscreen
 from ._lib import (SF_EVAL_BIG_ENDIAN, SF_EVAL_FAST_SINCOS, SF_EVAL_NAN_SCRUB,
-                   SF_EVAL_NT_STORES, SF_MAX_DIR, Context)
+                   SF_EVAL_NT_STORES, SF_MAX_DIR, SF_MAX_POINTS, Context)
 from .h5parm import H5parm, get_reference_station
 from .screen import Screen
 
@@ -39,11 +42,13 @@ def read_patch_names(skymodel_filename):
 
 
 class KLEvaluator:
-    """Device state for evaluating KL screens on one grid.  Owns its sf_ctx:
-    the basis and pixel grid it sets stay put whatever other screens or the
-    fit (which takes a ``private_context`` per call) set meanwhile."""
+    """Device state for evaluating KL screens on one grid and / or at a list
+    of positions.  Owns its sf_ctx: the basis, pixel grid and points it sets
+    stay put whatever other screens or the fit (which takes a
+    ``private_context`` per call) set meanwhile."""
 
-    def __init__(self, piercepoints, r_0, beta, x_coord, y_coord, device=0):
+    def __init__(self, piercepoints, r_0, beta, x_coord=None, y_coord=None,
+                 device=0):
         import torch
 
         self.torch = torch
@@ -51,7 +56,10 @@ class KLEvaluator:
         self.ctx = Context(device)
         self.pp = np.asarray(piercepoints, np.float64)
         self.D = self.pp.shape[0]
-        self.nx, self.ny = len(x_coord), len(y_coord)
+        if (x_coord is None) != (y_coord is None):
+            raise ValueError("give both grid coordinates or neither")
+        self.nx, self.ny = (0, 0) if x_coord is None else (len(x_coord), len(y_coord))
+        self.n_points = 0
         with torch.cuda.device(self.dev):
             self.ctx.set_stream(torch.cuda.current_stream(self.dev).cuda_stream)
             if self.D > SF_MAX_DIR:
@@ -59,7 +67,53 @@ class KLEvaluator:
                 self.ctx.set_piercepoints(self.pp, r_0, beta)
             else:
                 self.ctx.set_basis(self.pp, r_0, beta)
-            self.ctx.set_grid(x_coord, y_coord)
+            if x_coord is not None:
+                self.ctx.set_grid(x_coord, y_coord)
+
+    def set_points(self, xy):
+        """Bind P screen positions ``xy`` [P, 2] (piercepoint coordinates,
+        ``geometry.screen_xy``) for ``sample_device`` / ``sample_host``."""
+        torch = self.torch
+        with torch.cuda.device(self.dev):
+            self.ctx.set_stream(torch.cuda.current_stream(self.dev).cuda_stream)
+            self.ctx.set_points(xy)
+        self.n_points = self.ctx.points
+
+    def sample_device(self, coef_dev, xx_dev=None, yy_dev=None, out_dev=None,
+                      values=False, flags=SF_EVAL_NAN_SCRUB | SF_EVAL_FAST_SINCOS):
+        """coef_dev: device [S, D] float64 -> device [S, 4, P] float32 Jones
+        planes at the bound points (gain planes with ``xx_dev`` / ``yy_dev``),
+        or, with ``values``, the screen values [S, P] float64."""
+        torch = self.torch
+        S, P = coef_dev.shape[0], self.n_points
+        if out_dev is None:
+            out_dev = (torch.empty((S, P), dtype=torch.float64, device=self.dev)
+                       if values else
+                       torch.empty((S, 4, P), dtype=torch.float32, device=self.dev))
+        with torch.cuda.device(self.dev):
+            self.ctx.set_stream(torch.cuda.current_stream(self.dev).cuda_stream)
+            if values:
+                self.ctx.eval_point_values(coef_dev, S, out_dev)
+            else:
+                self.ctx.eval_points(coef_dev, S, out_dev, xx_dev, yy_dev, flags)
+        return out_dev
+
+    def sample_host(self, coef, amp_xx=None, amp_yy=None, values=False,
+                    flags=SF_EVAL_NAN_SCRUB | SF_EVAL_FAST_SINCOS):
+        """Host [..., D] coefficients -> host float32 [..., 4, P] planes, or
+        float64 [..., P] values."""
+        coef = np.asarray(coef)
+        lead = coef.shape[:-1]
+        c = self._upload(coef)
+        if values:
+            out = self.sample_device(c, values=True)
+            return out.cpu().numpy().reshape(lead + (self.n_points,))
+        if amp_xx is None:
+            out = self.sample_device(c, flags=flags)
+        else:
+            out = self.sample_device(c, self._upload(amp_xx), self._upload(amp_yy),
+                                     flags=flags)
+        return out.cpu().numpy().reshape(lead + (4, self.n_points))
 
     def eval_device(self, coef_dev, out_dev=None, flags=DEFAULT_FLAGS):
         """coef_dev: device [S, D] float64 -> device [S, 4, ny, nx] float32."""
@@ -132,6 +186,9 @@ class KLScreen(Screen):
         self.mid_ra = None
         self.mid_dec = None
         self._evaluators = {}
+        self._sampler = None
+        self.solset = None
+        self.ref_ind = None
 
     def fit(self):
         """Fit screens to the input solutions (kl_screen.py:61-155): phases
@@ -139,6 +196,7 @@ class KLScreen(Screen):
         solutions also the XX / YY log10 amplitudes (order
         min(12, max(3, round(D / 2))), 3 iterations, no order scaling)."""
         self._evaluators = {}  # a refit invalidates the evaluated basis
+        self._sampler = None
         h5 = H5parm(self.input_h5parm_filename)
         solset = h5.get_solset(self.input_solset_name)
         soltab_ph = solset.get_soltab(self.input_phase_soltab_name)
@@ -180,6 +238,10 @@ class KLScreen(Screen):
         self.piercepoints = np.array(st.piercepoint)
         self.mid_ra = st.attrs["midra"]
         self.mid_dec = st.attrs["middec"]
+        # the input and screen soltabs (in memory) and the reference station,
+        # for patch_errors
+        self.solset = solset
+        self.ref_ind = ref_ind
         h5.close()
 
     def get_memory_usage(self, cellsize_deg):
@@ -260,3 +322,151 @@ class KLScreen(Screen):
                 pipe.submit(slot, (s1 - s0) * per_slot, writer)
         finally:
             pipe.close()
+
+    def sampler(self):
+        """The evaluator ``sample`` binds its positions on (no pixel grid)."""
+        if self._sampler is None:
+            self._sampler = KLEvaluator(self.piercepoints, self.r_0, self.beta_val,
+                                        device=self.device)
+        return self._sampler
+
+    def sample(self, ra_deg, dec_deg, cellsize_deg=None, t_start=0, t_stop=None,
+               values=False, max_batch_bytes=1 << 30):
+        """The screens at sky positions, without building the cube.
+
+        With ``cellsize_deg``: what the a-term cube of that cell size holds at
+        the pixel containing each position (``geometry.patch_pixels``: the
+        cube entry ``[..., iy, ix]``, i.e. the screen at ``(X[ix], Y[iy])`` of
+        ``geometry.grid_coords``, Q8); positions outside the image give NaN
+        columns.  Without it: the screen at the exact position
+        (``geometry.screen_xy``).
+
+        Returns float64 ``[t_stop - t_start, F, A, 4, P]`` -- the planes of
+        ``make_matrix`` (raw, not NaN-scrubbed, float32 rounding) -- or, with
+        ``values``, the phase screen itself ``[t_stop - t_start, F, A, P]`` in
+        the fit's units (fp64).  Runs in device batches of whole time rows of
+        at most ``max_batch_bytes`` (coefficients + output), so the call's
+        device footprint does not grow with the number of times."""
+        ra = np.atleast_1d(np.asarray(ra_deg))
+        de = np.atleast_1d(np.asarray(dec_deg))
+        if ra.shape != de.shape or ra.ndim != 1:
+            raise ValueError("ra_deg and dec_deg: equal-length 1-D arrays")
+        n_pos = ra.shape[0]
+        if cellsize_deg is None:
+            x, y = geometry.screen_xy(ra, de, self.mid_ra, self.mid_dec)
+            inside = np.isfinite(x) & np.isfinite(y)
+        else:
+            ix, iy, inside = geometry.patch_pixels(ra, de, self.rad, self.dec,
+                                                   self.width_ra, cellsize_deg)
+            gx, gy = geometry.grid_coords(self.rad, self.dec, self.width_ra,
+                                          cellsize_deg, self.mid_ra, self.mid_dec)
+            x = gx[np.where(inside, ix, 0)]
+            y = gy[np.where(inside, iy, 0)]
+        xy = np.stack([np.where(inside, x, 0.0), np.where(inside, y, 0.0)], axis=1)
+        vals = np.asarray(self.vals_ph)
+        n_t, n_f, n_a, D = vals.shape
+        t_stop = n_t if t_stop is None else min(int(t_stop), n_t)
+        t_start = int(t_start)
+        if not 0 <= t_start <= t_stop:
+            raise ValueError(f"times [{t_start}, {t_stop}) outside 0..{n_t}")
+        gain = not self.phase_only and not values
+        shape = (t_stop - t_start, n_f, n_a) + ((n_pos,) if values else (4, n_pos))
+        out = np.full(shape, np.nan)
+        if t_stop == t_start or not inside.any():
+            return out
+        ev = self.sampler()
+        flags = SF_EVAL_FAST_SINCOS  # raw planes: no NaN scrub (make_matrix)
+        live = np.nonzero(inside)[0]
+        for p0 in range(0, live.size, SF_MAX_POINTS):
+            sel = live[p0:p0 + SF_MAX_POINTS]
+            P = sel.size
+            ev.set_points(xy[sel])
+            row_bytes = n_f * n_a * ((8 if values else 16) * P + 8 * D * (3 if gain else 1))
+            rows = max(1, int(max_batch_bytes // row_bytes))
+            for t0 in range(t_start, t_stop, rows):
+                t1 = min(t_stop, t0 + rows)
+                coef = ev._upload(vals[t0:t1])
+                if values:
+                    got = ev.sample_device(coef, values=True)
+                elif gain:
+                    amp = np.asarray(self.vals_amp)[t0:t1]
+                    got = ev.sample_device(coef, ev._upload(amp[..., 0]),
+                                           ev._upload(amp[..., 1]), flags=flags)
+                else:
+                    got = ev.sample_device(coef, flags=flags)
+                got = got.cpu().numpy().reshape((t1 - t0, n_f, n_a) + got.shape[1:])
+                out[t0 - t_start:t1 - t_start][..., sel] = got
+                del coef, got
+        return out
+
+    def patch_errors(self, cellsize_deg=None, max_batch_bytes=1 << 30):
+        """The reference's acceptance quantity (tests/test_fit_screens.py,
+        scripts/analyze_screens.py), per direction: float64 ``[D]``, the
+        maximum over times, frequencies, stations and the four planes of
+        |screen at the direction's position - expected|, where expected is
+        (a_xx cos phi, a_xx sin phi, a_yy cos phi, a_yy sin phi), phi the input
+        phase minus that of the reference station of ``fit`` and a the input
+        amplitudes on the phase grid (1 for phase-only screens).  Input
+        entries with zero weight or a non-finite value are left out; a
+        direction outside the image (``cellsize_deg`` given) or without any
+        usable entry gives NaN.  Positions are those of the solset's source
+        table; with ``cellsize_deg`` the screen is read at the pixel of the
+        cube of that cell size, without it at the exact position.  Needs
+        ``fit`` (``process``) on this object."""
+        if self.solset is None:
+            raise RuntimeError("patch_errors needs the input solutions: call "
+                               "fit() or process() first")
+        st = self.solset.get_soltab(self.input_phase_soltab_name)
+        names = st.get_axes_names()
+        order = [names.index(a) for a in ("time", "freq", "ant", "dir")]
+        val = np.transpose(np.asarray(st.val, np.float64), order)
+        wgt = np.transpose(np.asarray(st.weight), order)
+        n_t, n_f, n_a, D = val.shape
+        if not self.phase_only:
+            sa = self.solset.get_soltab(self.input_amplitude_soltab_name)
+            an = sa.get_axes_names()
+            ao = [an.index(a) for a in ("time", "freq", "ant", "dir", "pol")]
+            aval = np.transpose(np.asarray(sa.val, np.float64), ao)
+            awgt = np.transpose(np.asarray(sa.weight), ao)
+            # the input amplitudes on the phase grid: Screen.interpolate's
+            # nearest-sample gather along time, then frequency
+            from .screen import nearest_index
+            if aval.shape[0] != n_t:
+                it = (np.zeros(n_t, int) if aval.shape[0] == 1 else
+                      nearest_index(np.asarray(sa.time), self.times_ph))
+                aval, awgt = aval[it], awgt[it]
+            if aval.shape[1] != n_f:
+                jf = (np.zeros(n_f, int) if aval.shape[1] == 1 else
+                      nearest_index(np.asarray(sa.freq), self.freqs_ph))
+                aval, awgt = aval[:, jf], awgt[:, jf]
+        src = np.asarray(self.source_positions, np.float32)
+        ra, de = np.rad2deg(src[:, 0]), np.rad2deg(src[:, 1])  # float32 (Q11)
+        if cellsize_deg is None:
+            inside = np.ones(D, bool)
+        else:
+            inside = geometry.patch_pixels(ra, de, self.rad, self.dec,
+                                           self.width_ra, cellsize_deg)[2]
+        err = np.full(D, -np.inf)
+        row_bytes = n_f * n_a * D * (16 + 8 * (1 if self.phase_only else 3))
+        # host working set per time row: the sampled and the expected planes
+        rows = max(1, int(max_batch_bytes // (row_bytes + n_f * n_a * D * 96)))
+        for t0 in range(0, n_t, rows):
+            t1 = min(n_t, t0 + rows)
+            # position k is direction k's: the last axis of both arrays
+            got = self.sample(ra, de, cellsize_deg, t0, t1,
+                              max_batch_bytes=max_batch_bytes)
+            phi = val[t0:t1] - val[t0:t1, :, self.ref_ind:self.ref_ind + 1, :]
+            use = (wgt[t0:t1] != 0) & np.isfinite(val[t0:t1])
+            if self.phase_only:
+                axx = ayy = 1.0
+            else:
+                axx, ayy = aval[t0:t1, ..., 0], aval[t0:t1, ..., 1]
+                use &= ((awgt[t0:t1, ..., 0] != 0) & (awgt[t0:t1, ..., 1] != 0) &
+                        np.isfinite(axx) & np.isfinite(ayy))
+            want = (axx * np.cos(phi), axx * np.sin(phi),
+                    ayy * np.cos(phi), ayy * np.sin(phi))
+            for q in range(4):
+                diff = np.where(use, np.abs(got[:, :, :, q] - want[q]), -np.inf)
+                err = np.maximum(err, diff.reshape(-1, D).max(axis=0))
+        err[~inside | ~np.isfinite(err)] = np.nan
+        return err
