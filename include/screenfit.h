@@ -398,6 +398,31 @@ int sf_kl_eval_sums(sf_ctx* ctx, const double* coef_phase,
                     uint32_t* slot_sums);
 
 /*
+ * Screen VALUES on the pixel grid (kl_values.hip): what calculate_kl_screen
+ * (kl_screen.py:411-449) returns, and what the reference's "tec" a-term cube
+ * stores per pixel (processing_utils.py:187-190), without the cos / sin of the
+ * Jones planes:
+ *   out[(s % ring_slots)][ny][nx] = (float) sum_d Cpix[p][d] * coef[s][d]
+ * (device float32; rad, TECU or log10 amplitude, whatever was fitted).  The
+ * contraction is float64 with one cast at the store (Q12); pixel order and grid
+ * are sf_kl_eval's (Q8, sf_set_grid).  coef: device [S][D] float64.  Needs
+ * sf_set_grid on the geometry of sf_set_basis, sf_set_basis_wide or
+ * sf_set_piercepoints; one kernel serves 1 <= D <= SF_MAX_EVAL_DIR.
+ * flags: SF_EVAL_NAN_SCRUB (NaN -> 0.0f, the value whose Jones term is the
+ * 1 / 0 of the gain scrub), SF_EVAL_NT_STORES (honoured for 16-byte-aligned
+ * output and nx * ny % 4 == 0), SF_EVAL_BIG_ENDIAN; any other bit is
+ * SF_EINVAL.  Without the scrub a NaN coefficient gives a NaN plane for its
+ * slot and leaves the others alone.  ring_slots >= S gives every slot its own
+ * place; with a shorter ring an entry ends up holding the last slot that maps
+ * to it.  The output needs 4-byte alignment only (unaligned or odd-sized
+ * outputs take scalar stores).  SF_OPT_EVAL_MAX_BLOCKS, _GROUPS, _BANDS and
+ * _XCD_MAP are honoured.  Enqueued on the context stream; does not
+ * synchronise.
+ */
+int sf_kl_eval_values(sf_ctx* ctx, const double* coef, int64_t S, float* out,
+                      int64_t ring_slots, unsigned flags);
+
+/*
  * Screens sampled at positions (kl_points.hip): the value
  * calculate_kl_screen (kl_screen.py:411-449) gives at each of P positions,
  * without a pixel grid or a cube.  The point basis Cpix[p][d] =

@@ -730,6 +730,24 @@ int sf_kl_eval_point_values(sf_ctx* ctx, const double* coef, int64_t S,
   return sf::launch_eval_point_values(ctx, coef, S, values);
 }
 
+int sf_kl_eval_values(sf_ctx* ctx, const double* coef, int64_t S, float* out,
+                      int64_t ring, unsigned flags) {
+  SF_REQUIRE(ctx, SF_EINVAL, "sf_kl_eval_values: NULL context");
+  SF_REQUIRE(ctx->D > 0 && ctx->n_pix > 0 && ctx->d_cfrag, SF_EINVAL,
+             "sf_kl_eval_values: call sf_set_grid first");
+  SF_REQUIRE(coef && out && S >= 0 && ring >= 1, SF_EINVAL,
+             "sf_kl_eval_values: bad argument");
+  SF_REQUIRE((reinterpret_cast<uintptr_t>(out) & 3) == 0, SF_EINVAL,
+             "sf_kl_eval_values: output not 4-byte aligned");
+  SF_REQUIRE((flags & ~(SF_EVAL_NAN_SCRUB | SF_EVAL_NT_STORES | SF_EVAL_BIG_ENDIAN)) == 0,
+             SF_EINVAL,
+             "sf_kl_eval_values: flags other than SF_EVAL_NAN_SCRUB, "
+             "SF_EVAL_NT_STORES and SF_EVAL_BIG_ENDIAN");
+  if (S == 0) return SF_OK;
+  SF_HIP(hipSetDevice(ctx->device));
+  return sf::launch_eval_values(ctx, coef, S, out, ring, flags);
+}
+
 // scipy.ndimage._gaussian_kernel1d(sigma, 0, int(4 sigma + 0.5)) uploaded to
 // ctx->d_gw; R = 0 for sigma <= 1e-15 (the one weight 1.0).  The weights of
 // the last sigma stay on the device: repeated calls with the same sigma (every

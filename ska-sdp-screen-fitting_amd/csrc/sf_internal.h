@@ -235,6 +235,9 @@ int launch_eval(sf_ctx* ctx, const double* coef, const double* cxx,
 int launch_eval_wide(sf_ctx* ctx, const double* coef, const double* cxx,
                      const double* cyy, int64_t S, float* out, int64_t ring,
                      unsigned flags, unsigned* sums);
+// screen values on the pixel grid, any D (kl_values.hip)
+int launch_eval_values(sf_ctx* ctx, const double* coef, int64_t S, float* out,
+                       int64_t ring, unsigned flags);
 // screen positions (kl_points.hip): padded shapes of the point basis, its
 // kernel (d_pxy -> d_pfrag) and the slot-major evaluation at the points
 int points_ks_pad(int D);

@@ -12,3 +12,9 @@ def make_aterm_image(*args, **kwargs):
     """See :func:`ska_sdp_screen_fitting_amd.make_aterm_images.make_aterm_image`."""
     from .make_aterm_images import make_aterm_image as _impl
     return _impl(*args, **kwargs)
+
+
+def make_tec_aterm_image(*args, **kwargs):
+    """See :func:`ska_sdp_screen_fitting_amd.kl_tec_screen.make_tec_aterm_image`."""
+    from .kl_tec_screen import make_tec_aterm_image as _impl
+    return _impl(*args, **kwargs)

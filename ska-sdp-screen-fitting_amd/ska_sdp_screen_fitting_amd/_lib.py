@@ -72,6 +72,7 @@ EXPORTED = (
     "sf_set_grid", "sf_kl_eval", "sf_kl_eval_gain", "sf_kl_eval_sums",
     "sf_tess_fill", "sf_smooth",
     "sf_set_points", "sf_kl_eval_points", "sf_kl_eval_point_values",
+    "sf_kl_eval_values",
 )
 
 
@@ -162,6 +163,7 @@ def load_library(path=None):
             "sf_set_points": ([vp, vp, c_int], c_int),
             "sf_kl_eval_points": ([vp, vp, vp, vp, i64, vp, ctypes.c_uint], c_int),
             "sf_kl_eval_point_values": ([vp, vp, i64, vp], c_int),
+            "sf_kl_eval_values": ([vp, vp, i64, vp, i64, ctypes.c_uint], c_int),
         }
         for name, (args, res) in sig.items():
             fn = getattr(lib, name)
@@ -385,6 +387,17 @@ class Context:
             self._dev(out, np.float32, self._out_numel(S, ring), "out"), ring,
             int(flags)), "sf_kl_eval")
 
+    def eval_values(self, coef, S, out, ring_slots=None, flags=0):
+        """sf_kl_eval_values: the screen values themselves, float32
+        [min(S, ring), ny, nx] in the coefficients' own units (rad, TECU,
+        log10 amplitude), one plane per slot instead of the 4 Jones planes.
+        flags: SF_EVAL_NAN_SCRUB (NaN -> 0), SF_EVAL_NT_STORES,
+        SF_EVAL_BIG_ENDIAN."""
+        ring = max(int(S if ring_slots is None else ring_slots), 1)
+        _check(self.lib.sf_kl_eval_values(
+            self.h, self._dev(coef, np.float64, int(S) * self.D, "coef"), int(S),
+            self._dev(out, np.float32, self._out_numel(S, ring) // 4, "out"), ring,
+            int(flags)), "sf_kl_eval_values")
 
     def set_points(self, xy):
         """sf_set_points: P screen positions ``xy`` [P, 2] (x, y in

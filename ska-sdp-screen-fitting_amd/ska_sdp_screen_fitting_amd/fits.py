@@ -4,7 +4,8 @@ Produces the primary-HDU file that the reference builds with
 ``make_template_image`` (processing_utils.py:144-292) and fills in
 ``Screen.write`` (screen.py:331-382): BITPIX -32, axes
 [RA, DEC, MATRIX, ANTENNA, FREQ, TIME] (numpy order [time, freq, ant, 4, y, x]),
-big-endian float32, header cards in the reference's order.  Data are written
+big-endian float32, header cards in the reference's order; ``tec_header`` is
+the 5-axis dTEC layout without MATRIX ([time, freq, ant, y, x]).  Data are written
 in time-major chunks so a cube never has to exist whole in host memory.
 """
 
@@ -69,6 +70,25 @@ def aterm_header(rad, dec, nx, ny, cellsize_deg, freqs, times, n_ant):
               ("CUNIT6", "s"), ("CTYPE6", "TIME"), ("EQUINOX", 2000.0),
               ("TELESCOP", "LOFAR")]
     return cards
+
+
+def tec_header(rad, dec, nx, ny, cellsize_deg, freqs, times, n_ant):
+    """Header cards of make_template_image(..., aterm_type='tec')
+    (processing_utils.py:183-290): the dTEC cube has no MATRIX axis -- axes
+    [RA, DEC, ANTENNA, FREQ, TIME], numpy order [time, freq, ant, y, x]."""
+    cards = aterm_header(rad, dec, nx, ny, cellsize_deg, freqs, times, n_ant)
+    out = []
+    for k, v in cards:
+        if k == "NAXIS":
+            v = 5
+        elif k == "NAXIS3" or (k[-1] == "3" and k[:5] in ("CRVAL", "CDELT", "CRPIX",
+                                                       "CUNIT", "CTYPE")):
+            continue  # the MATRIX axis
+        elif k[-1] in "456" and k[:5] in ("NAXIS", "CRVAL", "CDELT", "CRPIX",
+                                          "CUNIT", "CTYPE"):
+            k = k[:5] + str(int(k[-1]) - 1)
+        out.append((k, v))
+    return out
 
 
 def header_bytes(cards):

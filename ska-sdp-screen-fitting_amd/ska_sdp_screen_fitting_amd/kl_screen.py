@@ -141,6 +141,29 @@ class KLEvaluator:
             self.ctx.eval_gain(coef_dev, xx_dev, yy_dev, S, out_dev, S, flags)
         return out_dev
 
+    def values_device(self, coef_dev, out_dev=None, flags=0):
+        """coef_dev: device [S, D] float64 -> device [S, ny, nx] float32, the
+        screen values themselves in the coefficients' units (``sf_kl_eval_values``:
+        fp64 contraction, one cast; NaN where a coefficient is NaN unless
+        ``flags`` scrub it to 0; plain stores: streaming stores measured no
+        faster for this kernel)."""
+        torch = self.torch
+        S = coef_dev.shape[0]
+        if out_dev is None:
+            out_dev = torch.empty((S, self.ny, self.nx), dtype=torch.float32,
+                                  device=self.dev)
+        with torch.cuda.device(self.dev):
+            self.ctx.set_stream(torch.cuda.current_stream(self.dev).cuda_stream)
+            self.ctx.eval_values(coef_dev, S, out_dev, S, flags)
+        return out_dev
+
+    def values_host(self, coef, flags=0):
+        """Host [..., D] coefficients -> host float32 [..., ny, nx] values."""
+        coef = np.asarray(coef)
+        lead = coef.shape[:-1]
+        out = self.values_device(self._upload(coef), flags=flags)
+        return out.cpu().numpy().reshape(lead + (self.ny, self.nx))
+
     def smooth_device(self, out_dev, smooth_pix, flags):
         """Screen.write's Gaussian (screen.py:353-362) in place on a device
         cube [S, 4, ny, nx]; scrub / byte swap in ``flags`` after it."""

@@ -1,0 +1,292 @@
+"""KL screens fitted to TEC solutions, rendered as the dTEC a-term cube.
+
+``KLTecScreen`` fits a ``tec`` soltab with ``stationscreen.run`` (the
+reference fits tec soltabs, stationscreen.py:858-1161, but has no screen class
+that renders them) and writes either
+
+* ``aterm_type="tec"``: the 5-axis cube of ``make_template_image(...,
+  aterm_type="tec")`` (processing_utils.py:144-292, its default layout):
+  ``[time][freq][ant][y][x]`` float32 dTEC values, no MATRIX axis -- the cube
+  an imager turns into phases itself, per channel.  The values come from
+  ``sf_kl_eval_values`` (csrc/kl_values.hip): fp64 contraction, one cast; or
+* ``aterm_type="gain"``: the ordinary 6-axis Jones cube at given frequencies.
+  The KL map is linear, so the phase screen at frequency nu is the screen of
+  the coefficients ``tec_coef * tec_to_phase / nu``: one broadcast on the
+  device, then ``sf_kl_eval``.
+"""
+
+import multiprocessing
+import os
+
+import numpy as np
+
+from . import fits
+from . import geometry
+from . import stationscreen
+from ._lib import SF_EVAL_BIG_ENDIAN, SF_EVAL_NAN_SCRUB
+from .h5parm import H5parm, get_reference_station
+from .kl_screen import DEFAULT_FLAGS, KLEvaluator, read_patch_names
+from .screen import Screen, nearest_index, time_chunks
+
+# phase [rad] = TEC_TO_PHASE * dTEC [TECU] / nu [Hz]: -8.4479745e9 is the usual
+# first-order ionospheric constant (-e^2 / (4 pi eps0 m_e c) * 1e16).  It is
+# NOT taken from the reference, which never converts tec screens to phases:
+# the imager's own convention decides, so every caller below takes it as a
+# parameter.
+TEC_TO_PHASE = -8.4479745e9
+
+
+def tec_to_phase_coef(tec_coef, freqs_hz, tec_to_phase=TEC_TO_PHASE,
+                      freq_index=None):
+    """Phase-screen coefficients of TEC-screen coefficients: torch tensor
+    ``tec_coef`` [T, F_tec, A, D] (any device) -> [T, F, A, D] with
+    ``out[:, f] = tec_coef[:, freq_index[f]] * tec_to_phase / freqs_hz[f]``.
+    ``freq_index`` defaults to 0 for every f (one tec frequency) and must be
+    given when the soltab has more."""
+    import torch
+
+    nu = torch.as_tensor(np.asarray(freqs_hz, np.float64), device=tec_coef.device)
+    if freq_index is None:
+        if tec_coef.shape[1] != 1:
+            raise ValueError("freq_index: needed for more than one tec frequency")
+        src = tec_coef  # [T, 1, A, D] x [F] -> [T, F, A, D]
+    else:
+        idx = torch.as_tensor(np.asarray(freq_index, np.int64), device=tec_coef.device)
+        src = tec_coef.index_select(1, idx)
+    return (src * (tec_to_phase / nu)[None, :, None, None]).contiguous()
+
+
+class KLTecScreen(Screen):
+    """KL screens of a ``tec`` soltab (values in TECU)."""
+
+    def __init__(self, name, h5parm_filename, skymodel_filename, rad, dec,
+                 width_ra, width_dec, solset_name="sol000",
+                 tec_soltab_name="tec000"):
+        super().__init__(name, h5parm_filename, skymodel_filename, rad, dec,
+                         width_ra, width_dec, solset_name=solset_name,
+                         phase_soltab_name=tec_soltab_name,
+                         amplitude_soltab_name=None)
+        self.input_tec_soltab_name = tec_soltab_name
+        self.height = None
+        self.beta_val = None
+        self.r_0 = None
+        self.piercepoints = None
+        self.mid_ra = None
+        self.mid_dec = None
+        self.ref_ind = None
+        self._evaluators = {}
+
+    def fit(self):
+        """Fit the tec screens as ``KLScreen.fit`` fits phases: reference
+        station among the first 10, order min(20, D - 1) scaled per station."""
+        self._evaluators = {}
+        h5 = H5parm(self.input_h5parm_filename)
+        solset = h5.get_solset(self.input_solset_name)
+        soltab_tec = solset.get_soltab(self.input_tec_soltab_name)
+        dirs = [str(d) for d in soltab_tec.dir]
+        if self.input_skymodel_filename is not None:
+            patches = set(read_patch_names(self.input_skymodel_filename))
+            missing = [d for d in dirs if d.strip("[]") not in patches]
+            if missing:
+                raise KeyError(f"directions not in the sky model: {missing}")
+        ref_ind = get_reference_station(soltab_tec, 10)
+        screen_order = min(20, len(dirs) - 1)
+        rc = stationscreen.run(soltab_tec, "tec_screen000", order=screen_order,
+                               ref_ant=ref_ind, scale_order=True, adjust_order=True,
+                               ncpu=self.ncpu or 0, device=self.device)
+        if rc != 0:
+            raise ValueError(f"soltab {self.input_tec_soltab_name!r} of type "
+                             f"{soltab_tec.get_type()!r} cannot be fitted")
+        st = solset.get_soltab("tec_screen000")
+        # (vals_ph / times_ph / freqs_ph: the names Screen.write's chunking reads)
+        self.vals_ph = st.val
+        self.times_ph = np.asarray(st.time)
+        self.freqs_ph = np.asarray(st.freq)
+        self.source_names = st.dir
+        self.source_dict = solset.get_source()
+        self.source_positions = [self.source_dict[s] for s in self.source_names]
+        self.station_names = st.ant
+        self.station_dict = solset.get_ant()
+        self.station_positions = [self.station_dict[s] for s in self.station_names]
+        self.height = st.attrs["height"]
+        self.beta_val = st.attrs["beta"]
+        self.r_0 = st.attrs["r_0"]
+        self.piercepoints = np.array(st.piercepoint)
+        self.mid_ra = st.attrs["midra"]
+        self.mid_dec = st.attrs["middec"]
+        self.ref_ind = ref_ind
+        h5.close()
+
+    def get_memory_usage(self, cellsize_deg, aterm_type="tec", n_freq=None):
+        """GB per time slot, stated as the reference states it for KL screens
+        (kl_screen.py:157-190: int() sizes, 8-byte values, /10 overhead,
+        x ncpu), for a [1, F, A, ny, nx] array ("gain": [1, F, A, 4, ny, nx])."""
+        ncpu = self.ncpu or multiprocessing.cpu_count()
+        ximsize = int(self.width_ra / cellsize_deg)
+        yimsize = int(self.width_dec / cellsize_deg)
+        n_f = len(self.freqs_ph) if n_freq is None else n_freq
+        planes = 4 if aterm_type == "gain" else 1
+        nbytes = 8 * n_f * len(self.station_names) * planes * yimsize * ximsize
+        return nbytes / 1024 ** 3 / 10 * ncpu
+
+    def evaluator(self, cellsize_deg):
+        key = float(cellsize_deg)
+        ev = self._evaluators.get(key)
+        if ev is None:
+            x, y = geometry.grid_coords(self.rad, self.dec, self.width_ra,
+                                        cellsize_deg, self.mid_ra, self.mid_dec)
+            ev = KLEvaluator(self.piercepoints, self.r_0, self.beta_val, x, y,
+                             self.device)
+            self._evaluators = {key: ev}
+        return ev
+
+    def make_matrix(self, t_start_index, t_stop_index, freq_ind, stat_ind,
+                    cellsize_deg, out_dir=None, ncpu=0, aterm_type="tec"):
+        """(t_stop - t_start, ny, nx) float64: the dTEC screen of one
+        (frequency, station), NaN where a coefficient is NaN, with the float32
+        rounding of the cube (Q12)."""
+        del out_dir, ncpu
+        if aterm_type != "tec":
+            raise ValueError('make_matrix renders aterm_type "tec" only')
+        coef = np.asarray(self.vals_ph)[t_start_index:t_stop_index, freq_ind, stat_ind, :]
+        return self.evaluator(cellsize_deg).values_host(coef).astype(np.float64)
+
+    def write_chunk(self, writer, g_start, g_stop, cellsize_deg,
+                    max_batch_bytes=1 << 30):
+        """dTEC values of times [g_start, g_stop), all (freq, station): device
+        batches of whole time rows in FITS byte order, NaN-scrubbed on the
+        device, streamed through pinned buffers (as KLScreen.write_chunk)."""
+        from .streaming import PinnedPipeline
+        torch = __import__("torch")
+        ev = self.evaluator(cellsize_deg)
+        vals = np.asarray(self.vals_ph)
+        n_f, n_a = vals.shape[1], vals.shape[2]
+        per_slot = 4 * ev.nx * ev.ny
+        row_bytes = n_f * n_a * per_slot
+        rows = max(1, int(max_batch_bytes // row_bytes))
+        rows = min(rows, g_stop - g_start)
+        coef = ev._upload(vals[g_start:g_stop])
+        # device buffers start 16-byte aligned: whole rows keep float4 stores
+        pipe = PinnedPipeline(torch, ev.dev, rows * row_bytes)
+        flags = SF_EVAL_NAN_SCRUB | SF_EVAL_BIG_ENDIAN
+        try:
+            for t0 in range(g_start, g_stop, rows):
+                t1 = min(g_stop, t0 + rows)
+                s0, s1 = (t0 - g_start) * n_f * n_a, (t1 - g_start) * n_f * n_a
+                slot, buf = pipe.device_buffer((s1 - s0) * per_slot)
+                out = buf.view(torch.float32).view(s1 - s0, ev.ny, ev.nx)
+                ev.values_device(coef[s0:s1], out, flags)
+                pipe.submit(slot, (s1 - s0) * per_slot, writer)
+        finally:
+            pipe.close()
+
+    def write_chunk_gain(self, writer, g_start, g_stop, cellsize_deg, freqs_hz,
+                         tec_to_phase, max_batch_bytes=1 << 30):
+        """Jones planes (cos, sin, cos, sin) of the phase tec_to_phase / nu x
+        dTEC at ``freqs_hz``, times [g_start, g_stop)."""
+        from .streaming import PinnedPipeline
+        torch = __import__("torch")
+        ev = self.evaluator(cellsize_deg)
+        vals = np.asarray(self.vals_ph)
+        n_a, D = vals.shape[2], vals.shape[3]
+        n_f = len(freqs_hz)
+        fidx = (np.zeros(n_f, int) if vals.shape[1] == 1 else
+                nearest_index(self.freqs_ph, freqs_hz))
+        per_slot = 16 * ev.nx * ev.ny
+        row_bytes = n_f * n_a * per_slot
+        rows = max(1, int(max_batch_bytes // row_bytes))
+        rows = min(rows, g_stop - g_start)
+        tec = torch.from_numpy(np.ascontiguousarray(vals[g_start:g_stop],
+                                                    np.float64)).to(ev.dev)
+        pipe = PinnedPipeline(torch, ev.dev, rows * row_bytes)
+        flags = DEFAULT_FLAGS | SF_EVAL_NAN_SCRUB | SF_EVAL_BIG_ENDIAN
+        try:
+            for t0 in range(g_start, g_stop, rows):
+                t1 = min(g_stop, t0 + rows)
+                n = (t1 - t0) * n_f * n_a
+                coef = tec_to_phase_coef(tec[t0 - g_start:t1 - g_start], freqs_hz,
+                                         tec_to_phase, fidx).view(n, D)
+                slot, buf = pipe.device_buffer(n * per_slot)
+                out = buf.view(torch.float32).view(n, 4, ev.ny, ev.nx)
+                ev.eval_device(coef, out, flags)
+                pipe.submit(slot, n * per_slot, writer)
+        finally:
+            pipe.close()
+
+    def write(self, out_dir, cellsize_deg, aterm_type="tec",
+              tec_to_phase=TEC_TO_PHASE, freqs_hz=None, ncpu=0):
+        """Write ``{name}_{g}.fits`` per time chunk (Screen.write's gap and
+        memory chunking) and ``{name}.txt`` listing them.
+
+        ``aterm_type="tec"``: the 5-axis dTEC cube [time][freq][ant][y][x] on
+        the soltab's frequency axis.  ``aterm_type="gain"``: the 6-axis Jones
+        cube at ``freqs_hz`` (default: the soltab's), phase = ``tec_to_phase``
+        x dTEC / nu; with several tec frequencies each output frequency takes
+        the nearest one's screens.  ``tec_to_phase`` (rad Hz / TECU) is the
+        imager-side convention, not something the reference defines: check it
+        against the consumer of the cube."""
+        if aterm_type not in ("tec", "gain"):
+            raise ValueError(f"unknown aterm_type {aterm_type!r}")
+        self.ncpu = ncpu
+        gain = aterm_type == "gain"
+        freqs = np.asarray(self.freqs_ph if freqs_hz is None or not gain else freqs_hz,
+                           np.float64).reshape(-1)
+        gaps_ind = time_chunks(self.times_ph, self.get_memory_usage(
+            cellsize_deg, aterm_type, len(freqs)))
+        nx, ny = self.grid_size(cellsize_deg)
+        n_ant = len(self.station_names)
+        header = fits.aterm_header if gain else fits.tec_header
+        outfiles = []
+        g_start = 0
+        for gnum, g_stop in enumerate(gaps_ind):
+            outfile = os.path.join(out_dir, f"{self.name}_{gnum}.fits")
+            cards = header(self.rad, self.dec, nx, ny, cellsize_deg, freqs,
+                           self.times_ph[g_start:g_stop], n_ant)
+            shape = (g_stop - g_start, len(freqs), n_ant) + ((4,) if gain else ()) + (ny, nx)
+            writer = fits.CubeWriter(outfile, cards, shape)
+            try:
+                if gain:
+                    self.write_chunk_gain(writer, g_start, g_stop, cellsize_deg,
+                                          freqs, tec_to_phase)
+                else:
+                    self.write_chunk(writer, g_start, g_stop, cellsize_deg)
+            finally:
+                writer.close()
+            outfiles.append(outfile)
+            g_start = g_stop
+        with open(os.path.join(out_dir, f"{self.name}.txt"), "w",
+                  encoding="utf8") as fh:
+            fh.writelines([o + "\n" for o in outfiles])
+        return outfiles
+
+
+def make_tec_aterm_image(h5parmfile, soltabname="tec000", outroot="",
+                         bounds_deg=None, bounds_mid_deg=None, skymodel=None,
+                         solsetname="sol000", padding_fraction=1.4,
+                         cellsize_deg=0.2, aterm_type="tec", ncpu=0,
+                         tec_to_phase=TEC_TO_PHASE, freqs_hz=None):
+    """``make_aterm_image`` for a tec soltab: fit KL screens to it and write
+    the dTEC cube (``aterm_type="tec"``) or the Jones cube at ``freqs_hz``
+    (``"gain"``, see ``KLTecScreen.write`` for ``tec_to_phase``).  Bounds and
+    padding as ``make_aterm_image``.  Returns None."""
+    if isinstance(bounds_deg, str):
+        bounds_deg = [float(f.strip()) for f in bounds_deg.strip("[]").split(";")]
+    if isinstance(bounds_mid_deg, str):
+        bounds_mid_deg = [float(f.strip()) for f in bounds_mid_deg.strip("[]").split(";")]
+    bounds_deg = list(bounds_deg)
+    if padding_fraction is not None:
+        padding_fraction = float(padding_fraction)
+        padding_ra = (bounds_deg[2] - bounds_deg[0]) * (padding_fraction - 1.0)
+        padding_dec = (bounds_deg[3] - bounds_deg[1]) * (padding_fraction - 1.0)
+        bounds_deg[0] -= padding_ra
+        bounds_deg[1] -= padding_dec
+        bounds_deg[2] += padding_ra
+        bounds_deg[3] += padding_dec
+    cellsize_deg = float(cellsize_deg)
+    width_deg = bounds_deg[3] - bounds_deg[1]
+    screen = KLTecScreen(os.path.basename(outroot), h5parmfile, skymodel,
+                         bounds_mid_deg[0], bounds_mid_deg[1], width_deg, width_deg,
+                         solset_name=solsetname, tec_soltab_name=soltabname)
+    screen.process(ncpu=ncpu)
+    screen.write(os.path.dirname(outroot), cellsize_deg, aterm_type=aterm_type,
+                 tec_to_phase=tec_to_phase, freqs_hz=freqs_hz, ncpu=ncpu)
