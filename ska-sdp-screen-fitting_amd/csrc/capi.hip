@@ -66,6 +66,18 @@ void drop_wide(sf_ctx* ctx) {
   ctx->wide_ws_cap = ctx->wide_w_cap = ctx->wide_o_cap = 0;
 }
 
+// No geometry, no grid, no points, wide state dropped: the context while a
+// new geometry is being bound, and what a failure on the way leaves (never a
+// D that points at freed buffers, nor a grid or points of another geometry).
+void drop_geometry(sf_ctx* ctx) {
+  ctx->D = 0;
+  ctx->has_basis = 0;
+  drop_wide(ctx);
+  ctx->nx = ctx->ny = 0;
+  ctx->n_pix = 0;
+  ctx->n_points = 0;
+}
+
 #define SF_TRY(x)              \
   do {                         \
     int rc_ = (x);             \
@@ -339,14 +351,7 @@ int sf_set_basis(sf_ctx* ctx, const double* pp, int D, double r0,
   SF_REQUIRE(r0 > 0.0, SF_EINVAL, "sf_set_basis: r0 must be > 0");
   SF_HIP(hipSetDevice(ctx->device));
   SF_HIP(hipStreamSynchronize(ctx->stream));
-  // invalidate basis and grid until the new basis is complete: a failure
-  // below must not leave a context whose D points at freed buffers
-  ctx->D = 0;
-  ctx->has_basis = 0;
-  drop_wide(ctx);
-  ctx->nx = ctx->ny = 0;
-  ctx->n_pix = 0;
-  ctx->n_points = 0;
+  drop_geometry(ctx);  // until the new basis is complete
   SF_TRY(dev_alloc(&ctx->d_pp, (size_t)3 * D));
   SF_TRY(dev_alloc(&ctx->d_c, (size_t)D * D));
   SF_TRY(dev_alloc(&ctx->d_pinv, (size_t)D * D));
@@ -377,14 +382,9 @@ int sf_set_piercepoints(sf_ctx* ctx, const double* pp, int D, double r0,
   SF_REQUIRE(r0 > 0.0, SF_EINVAL, "sf_set_piercepoints: r0 must be > 0");
   SF_HIP(hipSetDevice(ctx->device));
   SF_HIP(hipStreamSynchronize(ctx->stream));
-  // as sf_set_basis: no geometry and no grid until the new one is complete;
-  // the eigen-basis buffers of an earlier sf_set_basis are not this D's
-  ctx->D = 0;
-  ctx->has_basis = 0;
-  drop_wide(ctx);
-  ctx->nx = ctx->ny = 0;
-  ctx->n_pix = 0;
-  ctx->n_points = 0;
+  // as sf_set_basis; the eigen-basis buffers of an earlier sf_set_basis are
+  // not this D's
+  drop_geometry(ctx);
   SF_TRY(dev_alloc(&ctx->d_pp, (size_t)3 * D));
   SF_HIP(hipMemcpy(ctx->d_pp, pp, sizeof(double) * 3 * D,
                    hipMemcpyHostToDevice));
@@ -407,7 +407,7 @@ int sf_set_basis_wide(sf_ctx* ctx, const double* pp, int D, double r0,
   SF_TRY(sf_set_piercepoints(ctx, pp, D, r0, beta));
   // ... then C, pinv(C), U and the eigenvalues; until they are complete the
   // context has no geometry at all
-  ctx->D = 0;
+  drop_geometry(ctx);
   SF_TRY(dev_alloc(&ctx->d_c, (size_t)D * D));
   SF_TRY(dev_alloc(&ctx->d_pinv, (size_t)D * D));
   SF_TRY(dev_alloc(&ctx->d_u, (size_t)D * D));

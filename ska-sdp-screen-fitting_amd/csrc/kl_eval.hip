@@ -32,23 +32,13 @@
 // k-step count; the kernels and their launch templates are in
 // kl_eval_impl.h, instantiated per KS in kl_eval_ks1..5.hip.
 
+#include "kl_cov.h"
 #include "kl_eval_impl.h"
 
 namespace sf {
 
 // launch_eval_pick<KS> is instantiated in kl_eval_ks*.hip
 SF_EVAL_KS_LIST(SF_EVAL_EXTERN)
-
-__device__ inline double pix_cov(double ppx, double ppy, double ppz, double x,
-                                 double y, double r0sq, double half_beta) {
-#pragma clang fp contract(off)
-  // numpy: sum(square(PIERCEPOINTS - (x, y, 0)), axis=1) -> ((.)+(.))+(.)
-  const double dx = ppx - x;
-  const double dy = ppy - y;
-  const double dz = ppz - 0.0;
-  const double d2 = (dx * dx + dy * dy) + dz * dz;
-  return -pow(d2 / r0sq, half_beta) / 2.0;
-}
 
 // Cpix in MFMA B-fragment order: [wave pixel block][kstep][tile][lane].
 __global__ __launch_bounds__(256) void kl_cpix_kernel(
@@ -67,8 +57,8 @@ __global__ __launch_bounds__(256) void kl_cpix_kernel(
   double v = 0.0;
   if (p < (int64_t)nx * ny && d < D) {
     const int i = (int)(p % nx), j = (int)(p / nx);
-    v = pix_cov(pp[3 * d], pp[3 * d + 1], pp[3 * d + 2], xs[i], ys[j],
-                r0 * r0, beta / 2.0);
+    v = kl_cov(pp[3 * d], pp[3 * d + 1], pp[3 * d + 2], xs[i], ys[j], 0.0,
+               r0 * r0, beta / 2.0);
   }
   cfrag[e] = v;
 }
@@ -88,7 +78,7 @@ int launch_cpix(sf_ctx* ctx, const double* d_x, const double* d_y) {
 // wave pixel block in v_mfma_i32_16x16x64_i8 B order -- lane l, byte jb holds
 // direction d = 16 (l >> 4) + jb of pixel column l & 15 of tile t, i.e. digit
 // i of rint(Cpix[p][d] * 2^36) (0 past D or the grid).  Cpix is
-// kl_cpix_kernel's value bit for bit (pix_cov).
+// kl_cpix_kernel's value bit for bit (kl_cov).
 // A value that is not finite or does not fit the 6 digits (the host's range
 // check is a bound, not a proof) sets *bad, and sf_set_grid keeps the fp64
 // contraction for the grid.
@@ -114,8 +104,8 @@ __global__ __launch_bounds__(256) void kl_cdig_kernel(
     int8_t val = 0;
     if (d < D && p < (int64_t)nx * ny) {
       const int ix = (int)(p % nx), iy = (int)(p / nx);
-      const double c = pix_cov(pp[3 * d], pp[3 * d + 1], pp[3 * d + 2], xs[ix], ys[iy],
-                               r0 * r0, beta / 2.0);
+      const double c = kl_cov(pp[3 * d], pp[3 * d + 1], pp[3 * d + 2], xs[ix], ys[iy], 0.0,
+                              r0 * r0, beta / 2.0);
       const double y = ldexp(c, kSigma);
       const bool fin = __builtin_isfinite(y) && fabs(y) < 4.6e18;  // llrint range
       int8_t dg[kDigits];

@@ -16,6 +16,7 @@
 
 #include <cmath>
 
+#include "kl_cov.h"
 #include "sf_internal.h"
 #include "sf_wave.h"
 
@@ -25,18 +26,6 @@ constexpr double kPinvAtol = 1e-3;  // pinv(rcond=1e-3), scipy>=1.7 semantics
 constexpr int kMaxSweeps = 40;
 
 __host__ __device__ inline int odd_ld(int n) { return n | 1; }
-
-// C[i][j] = -(|pp_i - pp_j|^2 / r0^2)^(beta/2) / 2 with numpy's evaluation
-// order ((dx^2 + dy^2) + dz^2), no contraction.
-__device__ inline double kl_cov(const double* pi, const double* pj,
-                                double r0sq, double half_beta) {
-#pragma clang fp contract(off)
-  const double dx = pi[0] - pj[0];
-  const double dy = pi[1] - pj[1];
-  const double dz = pi[2] - pj[2];
-  const double d2 = (dx * dx + dy * dy) + dz * dz;
-  return -pow(d2 / r0sq, half_beta) / 2.0;
-}
 
 // ---------------------------------------------------------------------------
 // basis: one wavefront. C, eigen-decomposition by Jacobi, U sorted by

@@ -24,21 +24,11 @@
 
 #include <cmath>
 
+#include "kl_cov.h"
 #include "kl_fit_wide.h"
 #include "sf_internal.h"
 
 namespace sf {
-
-// C[i][j] of kl_fit.hip's kl_cov: numpy's evaluation order, no contraction.
-__device__ inline double wide_cov(const double* pi, const double* pj,
-                                  double r0sq, double half_beta) {
-#pragma clang fp contract(off)
-  const double dx = pi[0] - pj[0];
-  const double dy = pi[1] - pj[1];
-  const double dz = pi[2] - pj[2];
-  const double d2 = (dx * dx + dy * dy) + dz * dz;
-  return -pow(d2 / r0sq, half_beta) / 2.0;
-}
 
 // ---------------------------------------------------------------------------
 // basis: one workgroup; a and v ([D][ld] each) in the global workspace `ws`
@@ -57,7 +47,7 @@ __global__ __launch_bounds__(kWideThreads) void kl_basis_wide_kernel(
   const double r0sq = r0 * r0, hb = beta / 2.0;
   if (i < D) {
     for (int j = w; j < D; j += kWideShares) {
-      const double c = wide_cov(pp + 3 * i, pp + 3 * j, r0sq, hb);
+      const double c = kl_cov(pp + 3 * i, pp + 3 * j, r0sq, hb);
       a[i * ld + j] = c;
       c_out[i * D + j] = c;
     }

@@ -13,21 +13,19 @@
 //     pixel axes replaced by the point index), values [S][P] float64, so the
 //     16 consecutive slots of a wave form ONE contiguous run of 256 P
 //     (128 P) bytes;
-//   * the point basis Cpix[p][d] (kl_points_cpix_kernel: pix_cov's expression
-//     in pix_cov's order, so a point at (X[i], Y[j]) carries the bits of the
-//     grid's entry for pixel (j, i)) is stored as v_mfma_f64_16x16x4_f64 B
+//   * the point basis Cpix[p][d] (kl_points_cpix_kernel: kl_cov against
+//     (x, y, 0) as kl_cpix_kernel, so a point at (X[i], Y[j]) carries the bits
+//     of the grid's entry for pixel (j, i)) is stored as v_mfma_f64_16x16x4_f64 B
 //     fragments [16-point tile][k-step][lane], zero-padded to whole passes of
 //     kPtTiles tiles and to kPtKC k-steps.  A workgroup copies all of it into
 //     LDS once when two workgroups of that size fit a CU, else every MFMA
 //     reads its fragment through L1 / L2 (P x D up to 4096 x 128: 4 MiB);
 //   * a wave takes 16 consecutive slots and walks the point tiles kPtTiles at
 //     a time; the k-loop runs ceil(D / 4) k-steps at run time (one kernel for
-//     D = 1..128, the coefficient fragments of the next trip loaded while the
-//     MFMAs of this one run, rows past S and directions past D from a clamped
-//     address and masked, as kl_eval_wide.hip);
+//     D = 1..128: rt_contract of kl_eval_rt.h, the wide kernel's loop);
 //   * three epilogues: Jones planes of phase screens (cos, sin, cos, sin),
-//     of gain screens (three contractions), both from the helpers of
-//     kl_eval_impl.h (exact reduction in revolutions + hardware sincos under
+//     of gain screens (three contractions), both by jones_row of
+//     kl_eval_rt.h (exact reduction in revolutions + hardware sincos under
 //     SF_EVAL_FAST_SINCOS, fp64 sincos otherwise, 10^x, NaN scrub), and the
 //     raw fp64 contraction (values: the coefficients' own units, no 1 / 2 pi
 //     round trip, no scrub -- NaN passes through);
@@ -38,7 +36,8 @@
 //     output pointer (4 bytes for planes, 8 for values) are.  Dead slot rows
 //     (S % 16) and dead point columns (P % 16) are never stored.
 
-#include "kl_eval_impl.h"
+#include "kl_cov.h"
+#include "kl_eval_rt.h"
 
 namespace sf {
 
@@ -47,17 +46,6 @@ constexpr int kPtPass = 16 * kPtTiles;    // points per pass
 constexpr int kPtKC = 2;                  // k-steps per trip of the k-loop
 constexpr int kPtWaves = 4;               // waves (16-slot groups) per workgroup
 constexpr int kPtPlanes = 0, kPtGain = 1, kPtValues = 2;
-
-// pix_cov of kl_eval.hip: the same expression in the same order
-__device__ inline double point_cov(double ppx, double ppy, double ppz, double x,
-                                   double y, double r0sq, double half_beta) {
-#pragma clang fp contract(off)
-  const double dx = ppx - x;
-  const double dy = ppy - y;
-  const double dz = ppz - 0.0;
-  const double d2 = (dx * dx + dy * dy) + dz * dz;
-  return -pow(d2 / r0sq, half_beta) / 2.0;
-}
 
 // Cpix of the points in MFMA B-fragment order [point tile][k-step][lane]:
 // lane l of (tile, kk) holds point 16 tile + (l & 15), direction 4 kk + (l >> 4)
@@ -75,8 +63,8 @@ __global__ __launch_bounds__(256) void kl_points_cpix_kernel(
   const int d = 4 * kk + (l >> 4);
   double v = 0.0;
   if (p < P && d < D)
-    v = point_cov(pp[3 * d], pp[3 * d + 1], pp[3 * d + 2], xy[2 * p], xy[2 * p + 1],
-                  r0 * r0, beta / 2.0);
+    v = kl_cov(pp[3 * d], pp[3 * d + 1], pp[3 * d + 2], xy[2 * p], xy[2 * p + 1], 0.0,
+               r0 * r0, beta / 2.0);
   pfrag[e] = v;
 }
 
@@ -114,7 +102,6 @@ __global__ __launch_bounds__(64 * kPtWaves) void kl_eval_points_kernel(
   // elements by which the output pointer is past a 16-byte boundary
   const int oa = (int)((reinterpret_cast<uintptr_t>(out_v) / sizeof(T)) & (O::kVec - 1));
   const bool scrub = flags & SF_EVAL_NAN_SCRUB;
-  const double sc_ph = MODE == kPtValues ? 1.0 : kInv2Pi;  // planes: phase in turns
   const double sx = FAST ? kLog2of10 : 1.0;
   const int dl = l >> 4;
   // every wave of the workgroup runs every trip of both loops (the barriers
@@ -125,64 +112,23 @@ __global__ __launch_bounds__(64 * kPtWaves) void kl_eval_points_kernel(
     const int64_t sa = s0 + (l & 15);
     const bool srow = sa < S;
     const int64_t roff = (srow ? sa : S - 1) * D;
-    const double* rp = coef + roff;
-    const double* rxp = GAIN ? coef_xx + roff : nullptr;
-    const double* ryp = GAIN ? coef_yy + roff : nullptr;
+    const double* const rows[kMaxSets] = {coef + roff, GAIN ? coef_xx + roff : nullptr,
+                                          GAIN ? coef_yy + roff : nullptr};
     const int64_t left = S - s0;
     const int n_rows = (left >= 16 ? 16 : left > 0 ? (int)left : 0) * O::kRowsPerSlot;
     for (int pt0 = 0; pt0 < n_pt; pt0 += kPtTiles) {
       // ---- contraction: 16 slots x the pass's kPtTiles x 16 points
-      v4d acc[kPtTiles], accx[GAIN ? kPtTiles : 1], accy[GAIN ? kPtTiles : 1];
-#pragma unroll
-      for (int t = 0; t < kPtTiles; ++t) {
-        acc[t] = v4d{0.0, 0.0, 0.0, 0.0};
-        if constexpr (GAIN) {
-          accx[t] = v4d{0.0, 0.0, 0.0, 0.0};
-          accy[t] = v4d{0.0, 0.0, 0.0, 0.0};
-        }
-      }
-      double rf[kPtKC], rx[GAIN ? kPtKC : 1], ry[GAIN ? kPtKC : 1];
-      auto load_raw = [&](int k0) {
-#pragma unroll
-        for (int j = 0; j < kPtKC; ++j) {
-          const int d = 4 * (k0 + j) + dl;
-          const int dc = d < D ? d : D - 1;
-          rf[j] = rp[dc];
-          if constexpr (GAIN) {
-            rx[j] = rxp[dc];
-            ry[j] = ryp[dc];
-          }
-        }
-      };
-      load_raw(0);
-#pragma unroll 1
-      for (int k0 = 0; k0 < ks_pad; k0 += kPtKC) {
-        double af[kPtKC], ax[GAIN ? kPtKC : 1], ay[GAIN ? kPtKC : 1];
-#pragma unroll
-        for (int j = 0; j < kPtKC; ++j) {
-          const bool ok = srow && 4 * (k0 + j) + dl < D;
-          af[j] = keep_if(ok, rf[j] * sc_ph);
-          if constexpr (GAIN) {
-            ax[j] = keep_if(ok, rx[j] * sx);
-            ay[j] = keep_if(ok, ry[j] * sx);
-          }
-        }
-        // the next trip's loads (the last trip reloads its own: no branch)
-        load_raw(k0 + kPtKC < ks_pad ? k0 + kPtKC : k0);
-#pragma unroll
-        for (int j = 0; j < kPtKC; ++j) {
-#pragma unroll
-          for (int t = 0; t < kPtTiles; ++t) {
-            const int bi = ((pt0 + t) * ks_pad + k0 + j) * 64 + l;
-            const double b = LDSB ? pt_sh[bi] : pfrag[bi];
-            acc[t] = __builtin_amdgcn_mfma_f64_16x16x4f64(af[j], b, acc[t], 0, 0, 0);
-            if constexpr (GAIN) {
-              accx[t] = __builtin_amdgcn_mfma_f64_16x16x4f64(ax[j], b, accx[t], 0, 0, 0);
-              accy[t] = __builtin_amdgcn_mfma_f64_16x16x4f64(ay[j], b, accy[t], 0, 0, 0);
-            }
-          }
-        }
-      }
+      v4d acc[GAIN ? 3 : 1][kPtTiles];  // phase, XX, YY
+      rt_contract<kPtKC, kPtTiles, GAIN ? 3 : 1>(
+          acc, rows, srow, D, ks_pad, dl,
+          [=](int s, double x) {
+            if constexpr (MODE == kPtValues) return x;  // the coefficients' own units
+            else return x * (s == 0 ? kInv2Pi : sx);    // phase in turns
+          },
+          [=](int k, int t) {
+            const int bi = ((pt0 + t) * ks_pad + k) * 64 + l;
+            return LDSB ? pt_sh[bi] : pfrag[bi];
+          });
       // ---- epilogue into the wave's stage: accumulator register r of lane l
       // is slot row (l >> 4) + 4 r, point column 16 t + (l & 15)
 #pragma unroll
@@ -191,55 +137,10 @@ __global__ __launch_bounds__(64 * kPtWaves) void kl_eval_points_kernel(
         if constexpr (MODE == kPtValues) {
 #pragma unroll
           for (int t = 0; t < kPtTiles; ++t)
-            stage[row * O::kLd + 16 * t + (l & 15)] = acc[t][r];
+            stage[row * O::kLd + 16 * t + (l & 15)] = acc[0][t][r];
         } else {
-          float fr[kPtTiles];
-          if constexpr (FAST) {
-            double rv[kPtTiles];
-#pragma unroll
-            for (int t = 0; t < kPtTiles; ++t) rv[t] = acc[t][r];
-            rev_reduce_n<kPtTiles>(fr, rv, !GAIN && scrub);
-          }
           float pv[4][kPtTiles];  // planes Re XX, Im XX, Re YY, Im YY
-          constexpr bool kScrubValues = GAIN || !FAST;
-          bool bad = false;
-#pragma unroll
-          for (int t = 0; t < kPtTiles; ++t) {
-            float sn, cs;
-            if constexpr (FAST) sincos_rev(fr[t], sn, cs);
-            else sincos_rev_f64(acc[t][r], sn, cs);
-            if constexpr (GAIN) {
-              if constexpr (FAST) {
-                const float ax = amp2f(accx[t][r]);
-                const float ay = amp2f(accy[t][r]);
-                pv[0][t] = ax * cs;
-                pv[1][t] = ax * sn;
-                pv[2][t] = ay * cs;
-                pv[3][t] = ay * sn;
-              } else {
-                // reference: A (fp64) * cos (fp64), one cast to float32
-                const double ax = exp10(accx[t][r]);
-                const double ay = exp10(accy[t][r]);
-                pv[0][t] = (float)(ax * (double)cs);
-                pv[1][t] = (float)(ax * (double)sn);
-                pv[2][t] = (float)(ay * (double)cs);
-                pv[3][t] = (float)(ay * (double)sn);
-              }
-            } else {
-              pv[0][t] = pv[2][t] = cs;
-              pv[1][t] = pv[3][t] = sn;
-            }
-            if (kScrubValues)
-              bad |= __builtin_isunordered(pv[0][t], pv[1][t]) |
-                     __builtin_isunordered(pv[2][t], pv[3][t]);
-          }
-          if (kScrubValues && scrub && __builtin_amdgcn_ballot_w64(bad) != 0) {
-#pragma unroll
-            for (int t = 0; t < kPtTiles; ++t)
-#pragma unroll
-              for (int q = 0; q < 4; ++q)
-                if (isnan(pv[q][t])) pv[q][t] = (q & 1) ? 0.0f : 1.0f;
-          }
+          jones_row<FAST, GAIN, kPtTiles>(pv, acc, r, scrub);
 #pragma unroll
           for (int q = 0; q < 4; ++q)
 #pragma unroll

@@ -8,7 +8,10 @@
 // 4 N^2 bytes per slot, a quarter of the Jones cube's stores for the same
 // MFMAs, so from D ~ 20 the fp64 MFMAs and not the stores bound it.
 //
-// One kernel for 1 <= D <= SF_MAX_EVAL_DIR, on kl_eval_wide.hip's shape:
+// One kernel for 1 <= D <= SF_MAX_EVAL_DIR, on kl_eval_wide.hip's shape (the
+// walk below is that kernel's, spelled out here too: routed through a shared
+// template with the stores as functors, this kernel measured 0.3-1 % slower,
+// profiles/rt_kloop_isa.txt):
 //   * the 4 waves of a workgroup share ONE 64-pixel wave block, whose Cpix
 //     fragments (sf_set_grid's ctx->d_cfrag, [kstep][tile][lane]) sit in LDS,
 //     the k-step count rounded up to a multiple of 2 with zero fragments
@@ -18,10 +21,10 @@
 //     evaluates every slot that lands there in ascending order: with a ring
 //     shorter than the call an entry ends up holding its last slot;
 //   * the contraction walks the k-steps 2 at a time at run time (one kernel
-//     for every D, no template on the k-step count): the coefficient fragments
-//     of a trip are one double per k-step, the B operands come from LDS per
-//     MFMA (v_mfma_f64_16x16x4_f64), and only the 4 accumulator tiles stay in
-//     registers across the loop -- in VGPRs: the unit is built with the VGPR
+//     for every D, no template on the k-step count): rt_contract of
+//     kl_eval_rt.h without a scale, the B operands from LDS per MFMA, and
+//     only the 4 accumulator tiles stay in registers across the loop -- in
+//     VGPRs: the unit is built with the VGPR
 //     form of the MFMAs (csrc/Makefile), since AGPR accumulators were copied
 //     to VGPRs and back on every trip of a run-time loop;
 //   * fp64 all the way, one cast at the store (Q12).  The integer-digit
@@ -32,7 +35,7 @@
 //     (trash block for dead rows) or scalar stores for grids with P % 4 != 0
 //     and outputs that are not 16-byte aligned.
 
-#include "kl_eval_impl.h"
+#include "kl_eval_rt.h"
 
 namespace sf {
 
@@ -82,37 +85,11 @@ __global__ __launch_bounds__(64 * kEvalWaves) void kl_values_kernel(
         // ---- contraction: 16 slots x the block's 64 pixels
         const int64_t sa = s0 + (l & 15);
         const bool srow = e0 + (l & 15) < ring && sa < S;
-        const double* rp = coef + (srow ? sa : S - 1) * D;
-        v4d acc[kTiles];
-#pragma unroll
-        for (int t = 0; t < kTiles; ++t) acc[t] = v4d{0.0, 0.0, 0.0, 0.0};
-        // raw fragments of k-steps k0, k0 + 1: unconditional loads of
-        // clamped addresses (load_coef's reasoning), masked when used
-        double rf[kValKC];
-        auto load_raw = [&](int k0) {
-#pragma unroll
-          for (int j = 0; j < kValKC; ++j) {
-            const int d = 4 * (k0 + j) + dl;
-            rf[j] = rp[d < D ? d : D - 1];
-          }
-        };
-        load_raw(0);
-#pragma unroll 1
-        for (int k0 = 0; k0 < ks_pad; k0 += kValKC) {
-          double af[kValKC];
-#pragma unroll
-          for (int j = 0; j < kValKC; ++j)
-            af[j] = keep_if(srow && 4 * (k0 + j) + dl < D, rf[j]);
-          // the next trip's loads (the last trip reloads its own: no branch)
-          load_raw(k0 + kValKC < ks_pad ? k0 + kValKC : k0);
-#pragma unroll
-          for (int j = 0; j < kValKC; ++j) {
-            const double* bk = val_bsh + ((k0 + j) * kTiles) * 64 + l;
-#pragma unroll
-            for (int t = 0; t < kTiles; ++t)
-              acc[t] = __builtin_amdgcn_mfma_f64_16x16x4f64(af[j], bk[t * 64], acc[t], 0, 0, 0);
-          }
-        }
+        const double* const row[kMaxSets] = {coef + (srow ? sa : S - 1) * D, nullptr, nullptr};
+        v4d acc[1][kTiles];
+        rt_contract<kValKC, kTiles, 1>(
+            acc, row, srow, D, ks_pad, dl, [](int, double x) { return x; },
+            [=](int k, int t) { return val_bsh[(k * kTiles + t) * 64 + l]; });
         // ---- epilogue: accumulator row r = 4 slot rows x this lane's 4 pixels
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
@@ -122,7 +99,7 @@ __global__ __launch_bounds__(64 * kEvalWaves) void kl_values_kernel(
           float pv[kTiles];
 #pragma unroll
           for (int t = 0; t < kTiles; ++t) {
-            float v = (float)acc[t][r];
+            float v = (float)acc[0][t][r];
             if (scrub && isnan(v)) v = 0.0f;
             pv[t] = be ? bswapf(v) : v;
           }
@@ -153,26 +130,14 @@ int launch_eval_values(sf_ctx* ctx, const double* coef, int64_t S, float* out,
   }
   // a ring longer than the call changes nothing (slot s -> entry s)
   if (ring > S) ring = S;
-  const int ks_pad = (ks + kValKC - 1) / kValKC * kValKC;
-  const size_t lds = (size_t)ks_pad * kTiles * 64 * sizeof(double);  // <= 64 KiB
-  const int64_t P = ctx->n_pix;
-  const int64_t n_wpb = ctx->n_pix_blocks * kEvalWaves;
-  // work items: (64-pixel block, chunk of `groups` 16-entry ring groups); one
-  // launch: past the dispatch limit the workgroups walk the items (eval_grid)
-  const int groups = eval_chunk_groups(n_wpb, ring, ctx->eval_groups ? ctx->eval_groups : 64, 4096);
-  if (ctx->eval_xcd_map > 0) flags |= kEvalXcdInterleave;
-  const unsigned fl = flags | eval_band_flags(ctx, n_wpb);
-  const bool vec4 = (P % 4 == 0) && ((reinterpret_cast<uintptr_t>(out) & 15) == 0);
-  const bool nt = (flags & SF_EVAL_NT_STORES) && vec4;
-  const int64_t n_sc = (ring + 16 * groups - 1) / (16 * groups);
-  const int64_t nblk = eval_grid(ctx, n_wpb, n_sc, 256);
+  const BlockWalkLaunch g = block_walk_launch(ctx, kValKC, ring, flags, out);
 #define SF_LAUNCH_VALUES(V, N)                                                   \
-  hipLaunchKernelGGL((kl_values_kernel<V, N>), dim3((unsigned)nblk),             \
-                     dim3(64 * kEvalWaves), lds, ctx->stream, ctx->d_cfrag,      \
-                     coef, ctx->D, ks, ks_pad, S, P, n_wpb, n_sc, groups, out,   \
-                     ring, fl, ctx->d_trash)
-  if (!vec4) SF_LAUNCH_VALUES(false, false);
-  else if (nt) SF_LAUNCH_VALUES(true, true);
+  hipLaunchKernelGGL((kl_values_kernel<V, N>), dim3((unsigned)g.nblk),           \
+                     dim3(64 * kEvalWaves), g.lds, ctx->stream, ctx->d_cfrag,    \
+                     coef, ctx->D, ks, g.ks_pad, S, ctx->n_pix, g.n_wpb, g.n_sc, \
+                     g.groups, out, ring, g.fl, ctx->d_trash)
+  if (!g.vec4) SF_LAUNCH_VALUES(false, false);
+  else if (g.nt) SF_LAUNCH_VALUES(true, true);
   else SF_LAUNCH_VALUES(true, false);
 #undef SF_LAUNCH_VALUES
   SF_HIP(hipGetLastError());
