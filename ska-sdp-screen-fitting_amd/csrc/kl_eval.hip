@@ -29,11 +29,12 @@
 //     D = 44; the register tile takes larger D, fp64 sincos and gain screens
 //     (profiles/round2c_eval_sweep.txt).
 // This unit holds the pixel basis, the kernel choice and the dispatch on the
-// k-step count; the kernels and their launch templates are in
-// kl_eval_impl.h, instantiated per KS in kl_eval_ks1..5.hip.
+// k-step count; the kernels are in kl_eval_impl.h, their launch layer (plans,
+// split loop, variant dispatch) in kl_eval_launch.h, instantiated per KS in
+// kl_eval_ks1..5.hip.
 
 #include "kl_cov.h"
-#include "kl_eval_impl.h"
+#include "kl_eval_launch.h"
 
 namespace sf {
 

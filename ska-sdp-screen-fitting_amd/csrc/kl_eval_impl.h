@@ -1,8 +1,9 @@
-// kl_eval_impl.h -- the evaluation kernels and their launch templates,
-// shared by kl_eval.hip (pixel basis, kernel choice, dispatch on the k-step
-// count) and the kl_eval_ks*.hip units that instantiate launch_eval_pick<KS>
-// for a few KS each, so the five units compile in parallel.  See kl_eval.hip
-// for the design notes.
+// kl_eval_impl.h -- the evaluation kernels (device code only; their host
+// side -- launch plans, the split loop, the variant dispatch -- is
+// kl_eval_launch.h), shared by kl_eval.hip (pixel basis, kernel choice,
+// dispatch on the k-step count) and the kl_eval_ks*.hip units that
+// instantiate launch_eval_pick<KS> for a few KS each, so the five units
+// compile in parallel.  See kl_eval.hip for the design notes.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -1293,518 +1294,5 @@ __global__ __launch_bounds__(64 * NW) void kl_eval_lds_kernel(
     }
   }  // workgroup walk
 }
-
-// Grid of an eval launch: one workgroup per (pixel block, slot chunk) up to
-// the dispatch limit of 2^32 work-items (kept at 2^31), a multiple of 8 so
-// the XCD mapping of eval_block holds for every item a workgroup walks.
-inline int64_t eval_grid(const sf_ctx* ctx, int64_t n_pb, int64_t n_sc,
-                         int threads) {
-  int64_t n = n_pb * n_sc;
-  if ((n_pb & 7) == 0) n = ((n + 7) / 8) * 8;
-  int64_t cap = ((int64_t)1 << 31) / threads;
-  if (ctx->eval_max_blocks > 0 && ctx->eval_max_blocks < cap)
-    cap = ctx->eval_max_blocks;
-  cap = cap < 8 ? 8 : cap & ~(int64_t)7;
-  return n < cap ? n : cap;
-}
-
-// 16-slot groups per (pixel block, slot chunk) work item: as many as keep
-// >= min_items items (the grid fills the chip), at most max_groups
-// (SF_OPT_EVAL_GROUPS, else 64 for the register tile, 16 for the LDS-staged
-// kernels).  Every item loads its pixel block's Cpix fragments once, so long
-// chunks keep that reload small against the item's output: at 512^2 x D = 50
-// the Cpix of one XCD's pixel blocks (13.6 MB) outgrows its 4 MiB L2, and 16
-// groups per item re-read 3.6 TB of it per 8.2 M-slot launch (FETCH_SIZE,
-// 10 % of the writes; 64 groups: 0.9 TB, +2 %); at 256^2 x D = 20 the slices
-// stay in L2 and 16 groups keep each XCD's coefficient rows there too
-// (profiles/round2e_eval_groups_ab.txt, round2f_eval_groups_bench.txt).
-inline int eval_chunk_groups(int64_t n_pb, int64_t S, int max_groups,
-                             int64_t min_items) {
-  int groups = max_groups;
-  while (groups > 1 && n_pb * ((S + 16 * groups - 1) / (16 * groups)) < min_items)
-    groups >>= 1;
-  return groups;
-}
-
-
-// Slots per launch that keep one workgroup per work item: the dispatch caps
-// a grid at 2^31 work-items (eval_grid); past that the workgroups would walk
-// several items each, which measured 3-8 % slower than one-shot workgroups
-// dispatched in slot order (profiles/round2k_eval_split.txt), so a call
-// longer than that is split into consecutive launches.
-inline int64_t eval_launch_slots(const sf_ctx* ctx, int64_t n_pb, int groups,
-                                 int threads) {
-  int64_t cap = ((int64_t)1 << 31) / threads;
-  if (ctx->eval_max_blocks > 0) return INT64_MAX;  // the walk test keeps one launch
-  const int64_t chunks = cap / n_pb;
-  return (chunks < 1 ? 1 : chunks) * 16 * groups;
-}
-
-template <int KS, int MINW>
-int launch_eval_ks(sf_ctx* ctx, const double* coef,
-                          const double* cxx, const double* cyy, int64_t S_all,
-                          float* out, int64_t ring, unsigned flags,
-                          unsigned* sums) {
-  const int64_t P = ctx->n_pix;
-  const int64_t n_pb = ctx->n_pix_blocks;
-  // (64 groups also at 512^2: 8 measured 0.725 vs 0.691 of 8 TB/s in
-  // tools/eval_variants.py but 0.703 vs 0.714 in the config-5 bench step,
-  // profiles/round3y_eval_items_512.txt, round3ad_c5_fp64_g8.json)
-  const int groups = eval_chunk_groups(n_pb, S_all, ctx->eval_groups ? ctx->eval_groups : 64, 2048);
-  const int64_t per = eval_launch_slots(ctx, n_pb, groups, 256);
-  // large grids (>= 1024 blocks of 256 px: 512^2 and up): auto bands of 128
-  // blocks with the XCD-interleaved map -- 512^2 x D = 50 0.706 -> 0.732 of
-  // 8 TB/s; 2, 4 or 16 bands and the contiguous map measured no better
-  // (profiles/round2u_eval_bands.txt)
-  const int auto_bands = n_pb >= 1024 ? (int)(n_pb / 128 < 128 ? n_pb / 128 : 128) : 1;
-  unsigned fl = flags | eval_band_flags(ctx, n_pb, auto_bands);
-  if (ctx->eval_xcd_map < 0 && ctx->eval_bands == 0 && auto_bands > 1)
-    fl |= kEvalXcdInterleave;
-  for (int64_t b = 0; b < S_all; b += per) {
-  const int64_t S = S_all - b < per ? S_all - b : per;
-  const int64_t n_sc = (S + 16 * groups - 1) / (16 * groups);
-  const int64_t nblk = eval_grid(ctx, n_pb, n_sc, 256);
-  const double* cb = coef + b * ctx->D;
-  const double* cxb = cxx ? cxx + b * ctx->D : nullptr;
-  const double* cyb = cyy ? cyy + b * ctx->D : nullptr;
-  unsigned* sb = sums ? sums + b : nullptr;
-  const bool vec4 = (P % 4 == 0) && ((reinterpret_cast<uintptr_t>(out) & 15) == 0);
-  const bool fast = flags & SF_EVAL_FAST_SINCOS;
-  const bool nt = flags & SF_EVAL_NT_STORES;
-  const bool gain = cxx != nullptr;
-  const bool be = flags & SF_EVAL_BIG_ENDIAN;
-  // float4 + fast sincos, 64-pixel blocks inside the grid and a ring of
-  // whole 16-slot groups: the direct-addressing kernel over the whole groups
-  // of the launch, the general one over a ragged tail (< 16 slots)
-  // (up to D = 44: at D = 50 it measured 2 % slower, like the fixed-point
-  // reduction -- profiles/round3o_eval_direct_ab.txt)
-  const bool direct = KS <= kMagicMaxKS && vec4 && fast && P % kWavePix == 0 &&
-                      ring % 16 == 0 && (b % ring) % 16 == 0;
-  const int64_t S_dir = direct ? (S & ~(int64_t)15) : 0;
-#define SF_LAUNCH_BD(V, F, N, G, B, DIR, SL, NSC, NBLK, OFF)                   \
-  hipLaunchKernelGGL((kl_eval_kernel<KS, MINW, V, F, N, G, false, B, DIR>),     \
-                     dim3((unsigned)(NBLK)), dim3(256), 0, ctx->stream,         \
-                     ctx->d_cfrag, cb + (OFF) * ctx->D,                        \
-                     cxb ? cxb + (OFF) * ctx->D : nullptr,                     \
-                     cyb ? cyb + (OFF) * ctx->D : nullptr, ctx->D, SL, P, n_pb, \
-                     NSC, groups, out, ring, (b + (OFF)) % ring, fl,           \
-                     sb ? sb + (OFF) : nullptr, ctx->d_trash, ctx->rev_thr, DigArgs{})
-#define SF_LAUNCH_B(V, F, N, G, B)                                              \
-  do {                                                                          \
-    if constexpr (KS <= kMagicMaxKS) {                                          \
-      if (S_dir > 0) {                                                          \
-        const int64_t nsc_d = (S_dir + 16 * groups - 1) / (16 * groups);        \
-        SF_LAUNCH_BD(V, F, N, G, B, true, S_dir, nsc_d,                        \
-                     eval_grid(ctx, n_pb, nsc_d, 256), (int64_t)0);            \
-      }                                                                         \
-    }                                                                           \
-    if (S > S_dir) {                                                            \
-      const int64_t nsc_t = (S - S_dir + 16 * groups - 1) / (16 * groups);      \
-      SF_LAUNCH_BD(V, F, N, G, B, false, S - S_dir, nsc_t,                     \
-                   eval_grid(ctx, n_pb, nsc_t, 256), S_dir);                   \
-    }                                                                           \
-  } while (0)
-#define SF_LAUNCH(V, F, N, G) \
-  SF_LAUNCH_BD(V, F, N, G, 2, false, S, n_sc, nblk, (int64_t)0)
-#define SF_LAUNCH_G(V, F, N) \
-  do {                       \
-    if (gain)                \
-      SF_LAUNCH(V, F, N, true); \
-    else                     \
-      SF_LAUNCH(V, F, N, false); \
-  } while (0)
-  // float4 + fast sincos (every hot call): the byte order compiled in
-#define SF_LAUNCH_GB(N)                                  \
-  do {                                                   \
-    if (gain) {                                          \
-      if (be) SF_LAUNCH_B(true, true, N, true, 1);       \
-      else SF_LAUNCH_B(true, true, N, true, 0);          \
-    } else {                                             \
-      if (be) SF_LAUNCH_B(true, true, N, false, 1);      \
-      else SF_LAUNCH_B(true, true, N, false, 0);         \
-    }                                                    \
-  } while (0)
-  if (vec4) {
-    if (fast) {
-      if (nt) SF_LAUNCH_GB(true); else SF_LAUNCH_GB(false);
-    } else {
-      if (nt) SF_LAUNCH_G(true, false, true); else SF_LAUNCH_G(true, false, false);
-    }
-  } else {
-    if (fast) SF_LAUNCH_G(false, true, false); else SF_LAUNCH_G(false, false, false);
-  }
-#undef SF_LAUNCH_GB
-#undef SF_LAUNCH_G
-#undef SF_LAUNCH
-#undef SF_LAUNCH_B
-#undef SF_LAUNCH_BD
-  SF_HIP(hipGetLastError());
-  }
-  return SF_OK;
-}
-
-// SHB register tile (phase screens, float4-aligned output): one workgroup
-// per (64-pixel wave block, chunk of 4 x 16 groups of 16 slots)
-template <int KS>
-int launch_eval_shb(sf_ctx* ctx, const double* coef, int64_t S_all,
-                           float* out, int64_t ring, unsigned flags,
-                           unsigned* sums) {
-  const int64_t P = ctx->n_pix;
-  const int64_t n_wpb = ctx->n_pix_blocks * kEvalWaves;
-  const int groups = eval_chunk_groups(n_wpb, S_all, ctx->eval_groups ? ctx->eval_groups : 64, 4096);
-  const int64_t per = eval_launch_slots(ctx, n_wpb, groups, 256);
-  for (int64_t b = 0; b < S_all; b += per) {
-  const int64_t S = S_all - b < per ? S_all - b : per;
-  const int64_t n_sc = (S + 16 * groups - 1) / (16 * groups);
-  const int64_t nblk = eval_grid(ctx, n_wpb, n_sc, 256);
-  const double* cb = coef + b * ctx->D;
-  unsigned* sb = sums ? sums + b : nullptr;
-  const bool fast = flags & SF_EVAL_FAST_SINCOS;
-  const bool nt = flags & SF_EVAL_NT_STORES;
-#define SF_LAUNCH_SHB(F, N)                                                     \
-  hipLaunchKernelGGL((kl_eval_kernel<KS, 4, true, F, N, false, true>),          \
-                     dim3((unsigned)nblk), dim3(256), 0, ctx->stream,           \
-                     ctx->d_cfrag, cb, nullptr, nullptr, ctx->D, S, P, n_wpb, \
-                     n_sc, groups, out, ring, b % ring,                         \
-                     flags | eval_band_flags(ctx, n_wpb), sb, ctx->d_trash,     \
-                     ctx->rev_thr, DigArgs{})
-  if (fast) {
-    if (nt) SF_LAUNCH_SHB(true, true); else SF_LAUNCH_SHB(true, false);
-  } else {
-    if (nt) SF_LAUNCH_SHB(false, true); else SF_LAUNCH_SHB(false, false);
-  }
-#undef SF_LAUNCH_SHB
-  SF_HIP(hipGetLastError());
-  }
-  return SF_OK;
-}
-
-// Slots per launch of the integer contraction: its per-slot digit rows
-// (384 B) live in a context buffer of at most this many slots; launches of
-// 1 M slots are ~0.7 s at 512^2 x D = 50, so the cut costs no measurable tail
-constexpr int64_t kDigChunk = (int64_t)1 << 20;
-
-inline int ensure_kdig(sf_ctx* ctx, int64_t slots) {
-  if (ctx->kdig_slots >= slots) return SF_OK;
-  // (hipFree waits for the device, so no reader of the old buffers remains)
-  (void)hipFree(ctx->d_kdig);
-  (void)hipFree(ctx->d_kflag);
-  ctx->d_kdig = nullptr;
-  ctx->d_kflag = nullptr;
-  ctx->kdig_slots = 0;
-  if (hipMalloc(reinterpret_cast<void**>(&ctx->d_kdig), (size_t)slots * kDigits * 64) != hipSuccess ||
-      hipMalloc(reinterpret_cast<void**>(&ctx->d_kflag), (size_t)slots) != hipSuccess) {
-    set_error("sf_kl_eval: hipMalloc of the integer-contraction digits failed");
-    return SF_ENOMEM;
-  }
-  ctx->kdig_slots = slots;
-  return SF_OK;
-}
-
-// Prepass of one integer-contraction launch: the digit rows and flags of S
-// slots.  The buffers are the context's, so a launch on another stream may
-// still be reading them: the prepass waits for the last reader first
-// (kdig_read, recorded by kdig_done after every integer launch; on the same
-// stream the wait is already satisfied by stream order).
-inline int run_kdig(sf_ctx* ctx, const double* cb, int64_t S) {
-  if (!ctx->kdig_read)
-    SF_HIP(hipEventCreateWithFlags(&ctx->kdig_read, hipEventDisableTiming));
-  else
-    SF_HIP(hipStreamWaitEvent(ctx->stream, ctx->kdig_read, 0));
-  hipLaunchKernelGGL(kl_kdig_kernel<0>, dim3((unsigned)((S + 3) / 4)), dim3(256), 0,
-                     ctx->stream, cb, ctx->D, S, kInv2Pi, ctx->d_kdig, ctx->d_kflag);
-  SF_HIP(hipGetLastError());
-  return SF_OK;
-}
-
-// after the launch that read the digits run_kdig wrote
-inline int kdig_done(sf_ctx* ctx) {
-  SF_HIP(hipEventRecord(ctx->kdig_read, ctx->stream));
-  return SF_OK;
-}
-
-inline DigArgs dig_args(const sf_ctx* ctx, int64_t off) {
-  DigArgs dg;
-  dg.cdig = reinterpret_cast<const v4i*>(ctx->d_cdig);
-  dg.kdig = ctx->d_kdig + off * kDigits * 64;
-  dg.kflag = ctx->d_kflag + off;
-  return dg;
-}
-
-template <int KS, int NW, int TPW, bool GAIN = false>
-int launch_eval_lds(sf_ctx* ctx, const double* coef, const double* cxx,
-                    const double* cyy, int64_t S_all, float* out, int64_t ring,
-                    unsigned flags, unsigned* sums) {
-  const int64_t P = ctx->n_pix;
-  const int64_t run = EvalLds<NW, TPW, GAIN>::kRun;
-  const int64_t n_pb = (P + run - 1) / run;
-  // Small grids (n_pb <= 64: 256^2 and below, pixel blocks dealt to the XCDs
-  // interleaved): the shortest items whose Cpix reload (8 x 4 KS bytes per
-  // pixel) stays <= ~1/3 of their output (16 x 16 g bytes per pixel):
-  // KS <= 2 -> 1 group, 3-5 -> 2, 6-11 -> 4, else 8.  Measured in the bench
-  // setting (profiles/round2l_eval_chunks.txt): 256^2 x D = 20 0.72 (16
-  // groups) -> 0.79 (2 groups) of 8 TB/s, 1 group 0.67; 128^2 x D = 7 0.61
-  // -> 0.75 (1 group).  Larger grids keep 16 (their Cpix outgrows L2 and the
-  // long items won at 512^2, round2k_eval_split.txt).
-  const int def_groups = n_pb > 64 ? 16 : KS <= 2 ? 1 : KS <= 5 ? 2 : KS <= 11 ? 4 : 8;
-  const int groups = eval_chunk_groups(n_pb, S_all,
-                                       ctx->eval_groups ? ctx->eval_groups : def_groups, 1024);
-  int64_t per = eval_launch_slots(ctx, n_pb, groups, 64 * NW);
-  // the integer-digit contraction: per-launch slot digits (run_kdig), at
-  // most kDigChunk slots per launch
-  const bool ic = !GAIN && eval_int_applies(ctx, false, flags,
-                                            (reinterpret_cast<uintptr_t>(out) & 15) == 0);
-  if (ic) {
-    const int64_t gs = 16 * (int64_t)groups;
-    const int64_t cap = kDigChunk < gs ? gs : (kDigChunk / gs) * gs;
-    if (per > cap) per = cap;
-    const int rc = ensure_kdig(ctx, S_all < per ? S_all : per);
-    if (rc != SF_OK) return rc;
-  }
-  for (int64_t b = 0; b < S_all; b += per) {
-  const int64_t S = S_all - b < per ? S_all - b : per;
-  const int64_t n_sc = (S + 16 * groups - 1) / (16 * groups);
-  const int64_t nblk = eval_grid(ctx, n_pb, n_sc, 64 * NW);
-  const double* cb = coef + b * ctx->D;
-  const double* cxb = GAIN ? cxx + b * ctx->D : nullptr;
-  const double* cyb = GAIN ? cyy + b * ctx->D : nullptr;
-  unsigned* sb = sums ? sums + b : nullptr;
-  if (ic) {
-    const int rc = run_kdig(ctx, cb, S);
-    if (rc != SF_OK) return rc;
-  }
-  // auto XCD map: interleave the pixel blocks over the XCDs when each XCD's
-  // contiguous eighth would be <= 8 blocks (measured: 256^2 at 4 KiB runs
-  // +2-3 %, 512^2 -3 %; profiles/round1e_eval_xcd_map.txt)
-  unsigned fl = flags;
-  if (ctx->eval_xcd_map < 0 && (n_pb & 7) == 0 && n_pb / 8 <= 8)
-    fl |= kEvalXcdInterleave;
-  fl |= eval_band_flags(ctx, n_pb);
-#define SF_LAUNCH_LDS(N, I)                                                             \
-  hipLaunchKernelGGL((kl_eval_lds_kernel<KS, NW, TPW, N, I, GAIN>), dim3((unsigned)nblk), \
-                     dim3(64 * NW), 0, ctx->stream, ctx->d_cfrag, cb, cxb, cyb, ctx->D,   \
-                     ctx->ksteps, S, P, n_pb, n_sc, groups, out, ring, b % ring, fl,      \
-                     ctx->eval_sleep, sb, ctx->rev_thr, I ? dig_args(ctx, 0) : DigArgs{})
-  // (the integer variant only where it can apply: D >= 45)
-  if (ic) {
-    if constexpr (KS >= 12 && !GAIN) {
-      if (flags & SF_EVAL_NT_STORES) SF_LAUNCH_LDS(true, true);
-      else SF_LAUNCH_LDS(false, true);
-    }
-  } else {
-    if (flags & SF_EVAL_NT_STORES) SF_LAUNCH_LDS(true, false);
-    else SF_LAUNCH_LDS(false, false);
-  }
-#undef SF_LAUNCH_LDS
-  SF_HIP(hipGetLastError());
-  if (ic) {
-    const int rc = kdig_done(ctx);
-    if (rc != SF_OK) return rc;
-  }
-  }
-  return SF_OK;
-}
-
-// The register tile on the integer-digit contraction (phase, D >= 45);
-// NWV = 4 (256-pixel workgroup blocks) or 8 (512, SF_OPT_EVAL_WG_WAVES)
-template <int KS, int NWV>
-int launch_eval_int_nw(sf_ctx* ctx, const double* coef, int64_t S_all, float* out,
-                       int64_t ring, unsigned flags, unsigned* sums) {
-  const int64_t P = ctx->n_pix;
-  constexpr int kThreads = 64 * NWV;
-  // workgroup pixel blocks of NWV x 64 pixels (the wave blocks of the Cpix /
-  // digit fragments are 64 pixels either way)
-  const int64_t n_pb = (ctx->n_pix_blocks * kEvalWaves + NWV - 1) / NWV;
-  const int64_t n_pb256 = ctx->n_pix_blocks;
-  // large grids (>= 1024 blocks of 256 px: 512^2 and up): items of 4 groups
-  // (the digit fragments are 6 KB per wave block, a quarter of the fp64 ones,
-  // so short items cost little reload): 512^2 x D = 50 0.691 (64 groups) ->
-  // 0.744 of 8 TB/s, 2 / 8 groups 0.723 / 0.731
-  // (profiles/round3y_eval_items_512.txt)
-  const int def_groups = n_pb256 >= 1024 ? 4 : 64;
-  const int groups = eval_chunk_groups(n_pb, S_all, ctx->eval_groups ? ctx->eval_groups : def_groups,
-                                       2048 * kEvalWaves / NWV);
-  const int64_t gs = 16 * (int64_t)groups;
-  int64_t per = eval_launch_slots(ctx, n_pb, groups, kThreads);
-  const int64_t cap = kDigChunk < gs ? gs : (kDigChunk / gs) * gs;
-  if (per > cap) per = cap;
-  {
-    const int rc = ensure_kdig(ctx, S_all < per ? S_all : per);
-    if (rc != SF_OK) return rc;
-  }
-  // bands / XCD map as the fp64 register tile (launch_eval_ks): bands of
-  // 128 x 256 pixels
-  const int auto_bands = n_pb256 >= 1024 ? (int)(n_pb256 / 128 < 128 ? n_pb256 / 128 : 128) : 1;
-  unsigned fl = flags | eval_band_flags(ctx, n_pb, auto_bands);
-  if (ctx->eval_xcd_map < 0 && ctx->eval_bands == 0 && auto_bands > 1)
-    fl |= kEvalXcdInterleave;
-  const bool nt = flags & SF_EVAL_NT_STORES;
-  const bool be = flags & SF_EVAL_BIG_ENDIAN;
-  for (int64_t b = 0; b < S_all; b += per) {
-    const int64_t S = S_all - b < per ? S_all - b : per;
-    const double* cb = coef + b * ctx->D;
-    unsigned* sb = sums ? sums + b : nullptr;
-    {
-      const int rc = run_kdig(ctx, cb, S);
-      if (rc != SF_OK) return rc;
-    }
-    // (direct addressing: measured 2 % slower at D = 50 with fp64, not used)
-    const int64_t nsc = (S + gs - 1) / gs;
-    const unsigned nblk = (unsigned)eval_grid(ctx, n_pb, nsc, kThreads);
-#define SF_LAUNCH_IC(N, B)                                                                 \
-  hipLaunchKernelGGL((kl_eval_kernel<KS, 2, true, true, N, false, false, B, false, true, NWV>), \
-                     dim3(nblk), dim3(kThreads), 0, ctx->stream, ctx->d_cfrag, cb, nullptr,     \
-                     nullptr, ctx->D, S, P, n_pb, nsc, groups, out, ring, b % ring, fl,         \
-                     sb, ctx->d_trash, ctx->rev_thr, dig_args(ctx, 0))
-    if constexpr (KS >= 12) {
-      if (nt) {
-        if (be) SF_LAUNCH_IC(true, 1); else SF_LAUNCH_IC(true, 0);
-      } else {
-        if (be) SF_LAUNCH_IC(false, 1); else SF_LAUNCH_IC(false, 0);
-      }
-    }
-#undef SF_LAUNCH_IC
-    SF_HIP(hipGetLastError());
-    {
-      const int rc = kdig_done(ctx);
-      if (rc != SF_OK) return rc;
-    }
-  }
-  return SF_OK;
-}
-
-template <int KS>
-int launch_eval_int(sf_ctx* ctx, const double* coef, int64_t S_all, float* out,
-                    int64_t ring, unsigned flags, unsigned* sums) {
-  if (ctx->eval_wg_waves == 8)
-    return launch_eval_int_nw<KS, 8>(ctx, coef, S_all, out, ring, flags, sums);
-  return launch_eval_int_nw<KS, kEvalWaves>(ctx, coef, S_all, out, ring, flags, sums);
-}
-
-// The integer-digit contraction on the SHB tile (SF_EVAL_KERNEL_SHB with the
-// integer contraction): the 4 waves of a workgroup share one 64-pixel block,
-// its pixel digits in LDS, and take its 16-slot groups round-robin
-template <int KS>
-int launch_eval_int_shb(sf_ctx* ctx, const double* coef, int64_t S_all, float* out,
-                        int64_t ring, unsigned flags, unsigned* sums) {
-  const int64_t P = ctx->n_pix;
-  const int64_t n_wpb = ctx->n_pix_blocks * kEvalWaves;
-  // groups per item: 4 per wave (the register tile's 4-group items)
-  const int groups = eval_chunk_groups(n_wpb, S_all, ctx->eval_groups ? ctx->eval_groups : 16, 4096);
-  const int64_t gs = 16 * (int64_t)groups;
-  int64_t per = eval_launch_slots(ctx, n_wpb, groups, 256);
-  const int64_t cap = kDigChunk < gs ? gs : (kDigChunk / gs) * gs;
-  if (per > cap) per = cap;
-  {
-    const int rc = ensure_kdig(ctx, S_all < per ? S_all : per);
-    if (rc != SF_OK) return rc;
-  }
-  // pixel bands as the register tile's (bands of 128 x 256 pixels)
-  const int64_t n_pb = ctx->n_pix_blocks;
-  const int auto_bands = n_pb >= 1024 ? (int)(n_pb / 128 < 128 ? n_pb / 128 : 128) : 1;
-  unsigned fl = flags | eval_band_flags(ctx, n_wpb, auto_bands);
-  if (ctx->eval_xcd_map < 0 && ctx->eval_bands == 0 && auto_bands > 1)
-    fl |= kEvalXcdInterleave;
-  const bool nt = flags & SF_EVAL_NT_STORES;
-  const bool be = flags & SF_EVAL_BIG_ENDIAN;
-  for (int64_t b = 0; b < S_all; b += per) {
-    const int64_t S = S_all - b < per ? S_all - b : per;
-    const double* cb = coef + b * ctx->D;
-    unsigned* sb = sums ? sums + b : nullptr;
-    {
-      const int rc = run_kdig(ctx, cb, S);
-      if (rc != SF_OK) return rc;
-    }
-    const int64_t nsc = (S + gs - 1) / gs;
-    const unsigned nblk = (unsigned)eval_grid(ctx, n_wpb, nsc, 256);
-#define SF_LAUNCH_ICS(N, B)                                                              \
-  hipLaunchKernelGGL((kl_eval_kernel<KS, 3, true, true, N, false, true, B, false, true>), \
-                     dim3(nblk), dim3(256), 0, ctx->stream, ctx->d_cfrag, cb, nullptr,   \
-                     nullptr, ctx->D, S, P, n_wpb, nsc, groups, out, ring, b % ring, fl, \
-                     sb, ctx->d_trash, ctx->rev_thr, dig_args(ctx, 0))
-    if constexpr (KS >= 12) {
-      if (nt) {
-        if (be) SF_LAUNCH_ICS(true, 1); else SF_LAUNCH_ICS(true, 0);
-      } else {
-        if (be) SF_LAUNCH_ICS(false, 1); else SF_LAUNCH_ICS(false, 0);
-      }
-    }
-#undef SF_LAUNCH_ICS
-    SF_HIP(hipGetLastError());
-    {
-      const int rc = kdig_done(ctx);
-      if (rc != SF_OK) return rc;
-    }
-  }
-  return SF_OK;
-}
-
-template <int KS>
-int launch_eval_pick(sf_ctx* ctx, const double* coef, const double* cxx,
-                            const double* cyy, int64_t S, float* out,
-                            int64_t ring, unsigned flags,
-                            unsigned* sums) {
-  const bool aligned = (reinterpret_cast<uintptr_t>(out) & 15) == 0;
-  const int v = pick_eval_kernel(ctx, cxx != nullptr, flags, aligned);
-  // the integer-digit contraction: the LDS-staged kernels take it themselves,
-  // the register tile through launch_eval_int
-  if (eval_int_applies(ctx, cxx != nullptr, flags, aligned)) {
-    if (v == SF_EVAL_KERNEL_TILE || v == SF_EVAL_KERNEL_TILE3)
-      return launch_eval_int<KS>(ctx, coef, S, out, ring, flags, sums);
-    if (v == SF_EVAL_KERNEL_SHB)
-      return launch_eval_int_shb<KS>(ctx, coef, S, out, ring, flags, sums);
-  }
-  // gain screens (round 6): the LDS-staged shapes whose three-plane tile
-  // fits LDS (pick_eval_kernel maps LDS16 to LDS16H), up to kGainLdsMaxKS
-  if (cxx != nullptr) {
-    if constexpr (KS <= kGainLdsMaxKS) {
-      switch (v) {
-        case SF_EVAL_KERNEL_LDS4:
-          return launch_eval_lds<KS, 4, 4, true>(ctx, coef, cxx, cyy, S, out, ring, flags, sums);
-        case SF_EVAL_KERNEL_LDS8:
-          return launch_eval_lds<KS, 8, 4, true>(ctx, coef, cxx, cyy, S, out, ring, flags, sums);
-        case SF_EVAL_KERNEL_LDS8H:
-          return launch_eval_lds<KS, 8, 2, true>(ctx, coef, cxx, cyy, S, out, ring, flags, sums);
-        case SF_EVAL_KERNEL_LDS16H:
-          return launch_eval_lds<KS, 16, 2, true>(ctx, coef, cxx, cyy, S, out, ring, flags, sums);
-        default:
-          break;
-      }
-    }
-    // (pick_eval_kernel gives gain screens no other LDS-staged shape)
-    if (v != SF_EVAL_KERNEL_TILE && v != SF_EVAL_KERNEL_TILE3) {
-      set_error("sf_kl_eval_gain: no LDS-staged gain kernel for this shape");
-      return SF_EINVAL;
-    }
-  }
-  switch (v) {
-    case SF_EVAL_KERNEL_LDS4:
-      return launch_eval_lds<KS, 4, 4>(ctx, coef, nullptr, nullptr, S, out, ring, flags, sums);
-    case SF_EVAL_KERNEL_LDS8:
-      return launch_eval_lds<KS, 8, 4>(ctx, coef, nullptr, nullptr, S, out, ring, flags, sums);
-    case SF_EVAL_KERNEL_LDS16:
-      return launch_eval_lds<KS, 16, 4>(ctx, coef, nullptr, nullptr, S, out, ring, flags, sums);
-    case SF_EVAL_KERNEL_LDS8H:
-      return launch_eval_lds<KS, 8, 2>(ctx, coef, nullptr, nullptr, S, out, ring, flags, sums);
-    case SF_EVAL_KERNEL_LDS16H:
-      return launch_eval_lds<KS, 16, 2>(ctx, coef, nullptr, nullptr, S, out, ring, flags, sums);
-    case SF_EVAL_KERNEL_SHB:
-      return launch_eval_shb<KS>(ctx, coef, S, out, ring, flags, sums);
-    case SF_EVAL_KERNEL_TILE3:
-      // below 8 k-steps the register tile fits 4 waves/SIMD anyway
-      return launch_eval_ks<KS, (KS >= 8 ? 3 : 2)>(ctx, coef, cxx, cyy, S, out,
-                                                   ring, flags, sums);
-    default:
-      return launch_eval_ks<KS, 2>(ctx, coef, cxx, cyy, S, out, ring, flags, sums);
-  }
-}
-
-#define SF_EVAL_PICK_ARGS                                                    \
-  sf_ctx* ctx, const double* coef, const double* cxx, const double* cyy,   \
-      int64_t S, float* out, int64_t ring, unsigned flags, unsigned* sums
-#define SF_EVAL_KS_LIST(X) \
-  X(1) X(2) X(3) X(4) X(5) X(6) X(7) X(8) X(9) X(10) X(11) X(12) X(13) X(14) X(15)
-#define SF_EVAL_EXTERN(k) extern template int launch_eval_pick<k>(SF_EVAL_PICK_ARGS);
-#define SF_EVAL_INSTANTIATE(k) template int launch_eval_pick<k>(SF_EVAL_PICK_ARGS);
 
 }  // namespace sf

@@ -1,5 +1,5 @@
-// kl_eval_ks1.hip -- launch_eval_pick<KS> for KS = 1, 2, 3, 4 (see kl_eval_impl.h).
-#include "kl_eval_impl.h"
+// kl_eval_ks1.hip -- launch_eval_pick<KS> for KS = 1, 2, 3, 4 (see kl_eval_launch.h).
+#include "kl_eval_launch.h"
 
 namespace sf {
 SF_EVAL_INSTANTIATE(1)

@@ -1,5 +1,5 @@
-// kl_eval_ks5.hip -- launch_eval_pick<KS> for KS = 13, 14, 15 (see kl_eval_impl.h).
-#include "kl_eval_impl.h"
+// kl_eval_ks5.hip -- launch_eval_pick<KS> for KS = 13, 14, 15 (see kl_eval_launch.h).
+#include "kl_eval_launch.h"
 
 namespace sf {
 SF_EVAL_INSTANTIATE(13)

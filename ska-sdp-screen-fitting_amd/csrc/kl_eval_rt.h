@@ -8,7 +8,7 @@
 // memory until late in the pipeline and costs registers (4 VGPRs measured in
 // the point kernel).
 #pragma once
-#include "kl_eval_impl.h"
+#include "kl_eval_launch.h"
 
 namespace sf {
 
@@ -157,7 +157,7 @@ inline BlockWalkLaunch block_walk_launch(const sf_ctx* ctx, int kc, int64_t ring
   g.fl = flags | eval_band_flags(ctx, g.n_wpb);
   g.vec4 = (ctx->n_pix % 4 == 0) && ((reinterpret_cast<uintptr_t>(out) & 15) == 0);
   g.nt = (flags & SF_EVAL_NT_STORES) && g.vec4;
-  g.n_sc = (ring + 16 * g.groups - 1) / (16 * g.groups);
+  g.n_sc = eval_chunks(ring, g.groups);
   g.nblk = eval_grid(ctx, g.n_wpb, g.n_sc, 256);
   return g;
 }

@@ -158,28 +158,18 @@ int launch_eval_wide(sf_ctx* ctx, const double* coef, const double* cxx,
   const BlockWalkLaunch g = block_walk_launch(ctx, kWideKC, ring, flags, out);
   const bool fast = flags & SF_EVAL_FAST_SINCOS;
   const bool gain = cxx != nullptr;
-#define SF_LAUNCH_WIDE(V, F, N, G)                                               \
-  hipLaunchKernelGGL((kl_eval_wide_kernel<V, F, N, G>), dim3((unsigned)g.nblk),  \
-                     dim3(64 * kEvalWaves), g.lds, ctx->stream, ctx->d_cfrag,    \
-                     coef, cxx, cyy, ctx->D, ks, g.ks_pad, S_all, ctx->n_pix,    \
-                     g.n_wpb, g.n_sc, g.groups, out, ring, g.fl, sums,           \
-                     ctx->d_trash)
-#define SF_LAUNCH_WIDE_G(V, F, N)              \
-  do {                                         \
-    if (gain) SF_LAUNCH_WIDE(V, F, N, true);   \
-    else SF_LAUNCH_WIDE(V, F, N, false);       \
-  } while (0)
-  if (g.vec4) {
-    if (fast) {
-      if (g.nt) SF_LAUNCH_WIDE_G(true, true, true); else SF_LAUNCH_WIDE_G(true, true, false);
-    } else {
-      if (g.nt) SF_LAUNCH_WIDE_G(true, false, true); else SF_LAUNCH_WIDE_G(true, false, false);
-    }
-  } else {
-    if (fast) SF_LAUNCH_WIDE_G(false, true, false); else SF_LAUNCH_WIDE_G(false, false, false);
-  }
-#undef SF_LAUNCH_WIDE_G
-#undef SF_LAUNCH_WIDE
+  // 12 variants: NT stores are float4 stores (g.nt implies g.vec4)
+  with_bools(
+      [&](auto V, auto F, auto N, auto G) {
+        constexpr bool v = decltype(V)::value, n = decltype(N)::value;
+        if constexpr (v || !n)
+          hipLaunchKernelGGL(
+              (kl_eval_wide_kernel<v, decltype(F)::value, n, decltype(G)::value>),
+              dim3((unsigned)g.nblk), dim3(64 * kEvalWaves), g.lds, ctx->stream, ctx->d_cfrag,
+              coef, cxx, cyy, ctx->D, ks, g.ks_pad, S_all, ctx->n_pix, g.n_wpb, g.n_sc,
+              g.groups, out, ring, g.fl, sums, ctx->d_trash);
+      },
+      g.vec4, fast, g.nt, gain);
   SF_HIP(hipGetLastError());
   return SF_OK;
 }

@@ -131,15 +131,17 @@ int launch_eval_values(sf_ctx* ctx, const double* coef, int64_t S, float* out,
   // a ring longer than the call changes nothing (slot s -> entry s)
   if (ring > S) ring = S;
   const BlockWalkLaunch g = block_walk_launch(ctx, kValKC, ring, flags, out);
-#define SF_LAUNCH_VALUES(V, N)                                                   \
-  hipLaunchKernelGGL((kl_values_kernel<V, N>), dim3((unsigned)g.nblk),           \
-                     dim3(64 * kEvalWaves), g.lds, ctx->stream, ctx->d_cfrag,    \
-                     coef, ctx->D, ks, g.ks_pad, S, ctx->n_pix, g.n_wpb, g.n_sc, \
-                     g.groups, out, ring, g.fl, ctx->d_trash)
-  if (!g.vec4) SF_LAUNCH_VALUES(false, false);
-  else if (g.nt) SF_LAUNCH_VALUES(true, true);
-  else SF_LAUNCH_VALUES(true, false);
-#undef SF_LAUNCH_VALUES
+  // 3 variants: NT stores are float4 stores (g.nt implies g.vec4)
+  with_bools(
+      [&](auto V, auto N) {
+        constexpr bool v = decltype(V)::value, n = decltype(N)::value;
+        if constexpr (v || !n)
+          hipLaunchKernelGGL((kl_values_kernel<v, n>), dim3((unsigned)g.nblk),
+                             dim3(64 * kEvalWaves), g.lds, ctx->stream, ctx->d_cfrag, coef,
+                             ctx->D, ks, g.ks_pad, S, ctx->n_pix, g.n_wpb, g.n_sc, g.groups,
+                             out, ring, g.fl, ctx->d_trash);
+      },
+      g.vec4, g.nt);
   SF_HIP(hipGetLastError());
   return SF_OK;
 }

@@ -167,18 +167,40 @@ def test_int_grid_out_of_digit_range_keeps_fp64(ctx, dev):
         ctx.set_option(SF_OPT_EVAL_INT, -1)
 
 
-def test_int_many_launches_checksums(ctx, dev):
+@pytest.mark.parametrize("kernel,waves,name", [
+    ("AUTO", 0, "kl_eval_kernel"),
+    ("AUTO", 8, "kl_eval_kernel (8-wave workgroups)"),
+    ("LDS4", 0, "kl_eval_lds_kernel<4 waves>"),
+    ("SHB", 0, "kl_eval_kernel<Cpix in LDS>"),
+], ids=["auto-4waves", "auto-8waves", "lds4", "shb"])
+def test_int_many_launches_checksums(ctx, dev, kernel, waves, name):
     """A call of more slots than one integer launch holds (1 M slot digit
     buffer): 1.1 M slots into a 32-slot ring in checksum mode; the sums of the
     last slots (second launch) equal those of the same slots evaluated alone,
-    and the first slots' likewise."""
-    from ska_sdp_screen_fitting_amd._lib import SF_EVAL_FAST_SINCOS, SF_EVAL_NAN_SCRUB
+    and the first slots' likewise.  On every kernel family that takes the
+    integer contraction: the register tile at 4 and 8 waves, an LDS-staged
+    shape and the SHB tile share one split loop (kl_eval_launch.h)."""
+    from ska_sdp_screen_fitting_amd import _lib
+    from ska_sdp_screen_fitting_amd._lib import (
+        SF_EVAL_FAST_SINCOS, SF_EVAL_KERNEL_AUTO, SF_EVAL_NAN_SCRUB, SF_OPT_EVAL_KERNEL,
+        SF_OPT_EVAL_WG_WAVES)
     D, grid = 50, 32
     pp, x, y = grid_for(D, grid, seed=11)
     ctx.set_basis(pp)
     ctx.set_grid(x, y)
     flags = SF_EVAL_NAN_SCRUB | SF_EVAL_FAST_SINCOS
-    assert ctx.eval_contraction(flags) == "i8-digits"
+    try:
+        ctx.set_option(SF_OPT_EVAL_KERNEL, getattr(_lib, "SF_EVAL_KERNEL_" + kernel))
+        ctx.set_option(SF_OPT_EVAL_WG_WAVES, waves)
+        assert ctx.eval_kernel(flags) == name
+        assert ctx.eval_contraction(flags) == "i8-digits"
+        _many_launches_checksums(ctx, dev, D, grid, flags)
+    finally:
+        ctx.set_option(SF_OPT_EVAL_KERNEL, SF_EVAL_KERNEL_AUTO)
+        ctx.set_option(SF_OPT_EVAL_WG_WAVES, 0)
+
+
+def _many_launches_checksums(ctx, dev, D, grid, flags):
     S = 1_100_000
     g = torch.Generator(device=dev)
     g.manual_seed(5)
