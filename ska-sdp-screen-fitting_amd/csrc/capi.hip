@@ -53,17 +53,13 @@ int dev_alloc(T** p, size_t count) {
   return SF_OK;
 }
 
-// A new geometry: the workspace and state buffers of the wide fit
-// (kl_fit_wide.hip) were sized for the previous D.
+// A new geometry: the workspace of the wide fit (kl_fit_wide.hip) was sized
+// for the previous D.
 void drop_wide(sf_ctx* ctx) {
   ctx->wide = 0;
   hipFree(ctx->d_wide_ws);
-  hipFree(ctx->d_wide_w);
-  hipFree(ctx->d_wide_o);
   ctx->d_wide_ws = nullptr;
-  ctx->d_wide_w = nullptr;
-  ctx->d_wide_o = nullptr;
-  ctx->wide_ws_cap = ctx->wide_w_cap = ctx->wide_o_cap = 0;
+  ctx->wide_ws_cap = 0;
 }
 
 // No geometry, no grid, no points, wide state dropped: the context while a
@@ -116,8 +112,6 @@ int sf_destroy(sf_ctx* ctx) {
   hipFree(ctx->d_u);
   hipFree(ctx->d_eig);
   hipFree(ctx->d_wide_ws);
-  hipFree(ctx->d_wide_w);
-  hipFree(ctx->d_wide_o);
   hipFree(ctx->d_cfrag);
   hipFree(ctx->d_pxy);
   hipFree(ctx->d_pfrag);

@@ -7,9 +7,12 @@
 //   * kl_basis_kernel   <- _calculate_svd (stationscreen.py:390-430)
 //   * kl_skip_kernel    <- the (station, freq) block skip of
 //                          _process_single_freq (stationscreen.py:817-825)
-//   * kl_fit_kernel     <- _process_station (stationscreen.py:597-782) with
-//                          _fit_screen (:433-594), _flag_outliers (:303-350),
-//                          _circ_chi2 (:353-387) for one slot per wavefront.
+//   * kl_fit_general_kernel <- _process_station (stationscreen.py:597-782)
+//                          for one slot per wavefront, every outlier iteration
+//                          in one launch: the slot loop here, its steps
+//                          (_flag_outliers, _circ_chi2, the order walk) in
+//                          kl_fit_steps.h, _fit_screen (:433-594) with the
+//                          exact pinv in kl_fit_exact.h.
 // Every phase slot is independent (see oracle/kl.py for the argument), so a
 // slot is the unit of parallelism.
 #include <hip/hip_runtime.h>
@@ -17,15 +20,10 @@
 #include <cmath>
 
 #include "kl_cov.h"
+#include "kl_fit_exact.h"
 #include "sf_internal.h"
-#include "sf_wave.h"
 
 namespace sf {
-
-constexpr double kPinvAtol = 1e-3;  // pinv(rcond=1e-3), scipy>=1.7 semantics
-constexpr int kMaxSweeps = 40;
-
-__host__ __device__ inline int odd_ld(int n) { return n | 1; }
 
 // ---------------------------------------------------------------------------
 // basis: one wavefront. C, eigen-decomposition by Jacobi, U sorted by
@@ -53,8 +51,8 @@ __global__ __launch_bounds__(64) void kl_basis_kernel(
     }
   }
   lds_sync();
-  wave_jacobi(a, v, cs, pr, D, ld, kMaxSweeps);
-  wave_eig_order(a, D, ld, perm);
+  wave_jacobi(a, v, cs, pr, D, ld, kJacobiMaxSweeps);
+  eig_order(Group<1>{}, a, D, ld, perm);
   if (i < D) {
     for (int r = 0; r < D; ++r) u_out[i * D + r] = v[i * ld + perm[r]];
     const int pr = perm[i];
@@ -85,6 +83,8 @@ __global__ __launch_bounds__(64) void kl_skip_kernel(
   bool any_val = false, any_w = false;
   for (int t = 0; t < T; ++t) {
     if (d < D) {
+      // phase_ref (kl_fit_steps.h) with the block's (t, f) in hand: no
+      // division by A per element
       const int64_t base = ((int64_t)(t * F + f) * A) * D;
       double ph = phase[base + (int64_t)a * D + d];
       if (refph) ph -= refph[(int64_t)(t * F + f) * D + d];
@@ -103,7 +103,10 @@ __global__ __launch_bounds__(64) void kl_skip_kernel(
 // ---------------------------------------------------------------------------
 // per-slot fit
 // ---------------------------------------------------------------------------
+// Where the matrices of one wavefront's exact fit live (the X of
+// kl_fit_exact.h): everything in LDS, rows of stride ld.
 struct FitLds {
+  static constexpr bool kFused = true;
   // shared by the workgroup
   double* C;     // [D][ld]
   double* U;     // [D][ld], columns sorted
@@ -113,11 +116,23 @@ struct FitLds {
   double* M1;    // [D][ld] scratch
   double* M2;    // [D][ld] normal matrix / scratch
   double* lam;   // [64] eigenvalues of C_sub by rank
-  double* vec;   // [6][64] broadcast vectors
+  double* vecs;  // [6][64] broadcast vectors
   int* idx;      // [64] subset -> direction
   int* perm;     // [64] rank -> column of V
   double2* cs;   // [64] Jacobi rotations
   int2* pr;      // [64] + 64 int: Jacobi round pairs / partners
+  int ld;
+  __device__ double csym(int r, int q) const { return C[r * ld + q]; }
+  __device__ double u(int p, int k) const { return U[p * ld + k]; }
+  __device__ double eigv(int p) const { return eig[p]; }
+  __device__ double* vec(int k) const { return vecs + 64 * k; }
+  __device__ void jacobi(double* a, double* v, int n, int ld_) const {
+    wave_jacobi(a, v, cs, pr, n, ld_, kJacobiMaxSweeps);
+  }
+  __device__ void cholesky(double* g, int k, int ld_, double& b1, double& b2) const {
+    wave_cholesky_solve2(g, k, ld_, b1, b2);
+  }
+  __device__ void decomposed() const {}
 };
 
 __host__ __device__ inline size_t fit_shared_bytes(int D) {
@@ -127,279 +142,6 @@ __host__ __device__ inline size_t fit_wave_bytes(int D) {
   return (size_t)(3 * D * odd_ld(D) + 64 + 6 * 64) * sizeof(double) +
          (size_t)(64 + 64) * sizeof(int) + 64 * sizeof(double2) +
          96 * sizeof(int2);
-}
-
-struct SubsetState {
-  int n;        // number of unflagged directions
-  bool full;    // n == D: use the shared basis (quirk Q1)
-  double wmin;  // smallest unflagged weight
-};
-
-// Cache the basis of the unflagged subset (stationscreen.py:493-499).
-__device__ void setup_subset(const FitLds& L, int D, int ld, double w_d,
-                             SubsetState& st) {
-  const int d = lane();
-  const bool unfl = (d < D) && (w_d > 0.0);
-  const uint64_t mask = __ballot(unfl);
-  const int n = __popcll(mask);
-  st.n = n;
-  st.full = (n == D);
-  double wm = unfl ? w_d : INFINITY;
-  wm = -wave_max(-wm);
-  st.wmin = wm;
-  if (unfl) {
-    const int p = __builtin_amdgcn_mbcnt_hi((uint32_t)(mask >> 32),
-                                            __builtin_amdgcn_mbcnt_lo((uint32_t)mask, 0));
-    L.idx[p] = d;
-  }
-  lds_sync();
-  if (st.full) return;  // shared U / eig (already sorted)
-  if (n == 0) return;
-  // C_sub = C[idx][:, idx], eigen-decomposed in M1 / V
-  if (d < n) {
-    const int r = L.idx[d];
-    for (int q = 0; q < n; ++q) L.M1[d * ld + q] = L.C[r * ld + L.idx[q]];
-  }
-  lds_sync();
-  wave_jacobi(L.M1, L.V, L.cs, L.pr, n, ld, kMaxSweeps);
-  wave_eig_order(L.M1, n, ld, L.perm);
-  if (d < n) {
-    const int m = L.perm[d];
-    L.lam[d] = L.M1[m * ld + m];
-  }
-  lds_sync();
-}
-
-// column `rank` of the (sorted) U of the current subset, row p
-__device__ __forceinline__ double ucol(const FitLds& L, const SubsetState& st,
-                                       int ld, int p, int rank) {
-  return st.full ? L.U[p * ld + rank] : L.V[p * ld + L.perm[rank]];
-}
-
-// y = pinv(C_sub) x for x held one element per lane (lanes < n), through
-// the eigen-decomposition: y = sum_{|lam|>atol} u_r (u_r^T x) / lam_r.
-__device__ double apply_pinv(const FitLds& L, const SubsetState& st, int ld,
-                             double x, double* vtmp) {
-  const int p = lane();
-  const int n = st.n;
-  if (p < n) vtmp[p] = x;
-  lds_sync();
-  double t = 0.0;
-  if (p < n) {
-    for (int q = 0; q < n; ++q) t += ucol(L, st, ld, q, p) * vtmp[q];
-    const double lam = st.full ? L.eig[p] : L.lam[p];
-    t = (fabs(lam) > kPinvAtol) ? t / lam : 0.0;
-  }
-  lds_sync();
-  if (p < n) vtmp[p] = t;
-  lds_sync();
-  double y = 0.0;
-  if (p < n)
-    for (int r = 0; r < n; ++r) y += ucol(L, st, ld, p, r) * vtmp[r];
-  lds_sync();
-  return y;
-}
-
-// full-basis pinv (shared U / eig), x on lanes < D
-__device__ double apply_pinv_full(const FitLds& L, int D, int ld, double x,
-                                  double* vtmp) {
-  SubsetState full{D, true, 0.0};
-  return apply_pinv(L, full, ld, x, vtmp);
-}
-
-// y_p = sum_q C[idx p][idx q] x_q  (lanes < n)
-__device__ double apply_csub(const FitLds& L, int n, int ld, double x,
-                             double* vtmp) {
-  const int p = lane();
-  if (p < n) vtmp[p] = x;
-  lds_sync();
-  double y = 0.0;
-  if (p < n) {
-    const int r = L.idx[p];
-    for (int q = 0; q < n; ++q) y += L.C[r * ld + L.idx[q]] * vtmp[q];
-  }
-  lds_sync();
-  return y;
-}
-
-// One _fit_screen call (stationscreen.py:433-594) at order K.  Inputs per
-// direction lane d: phi_d, w_d.  Outputs per direction lane: white_d,
-// resid_d.
-__device__ void fit_screen(const FitLds& L, const SubsetState& st, int D,
-                           int ld, int K, int screen_type, double phi_d,
-                           double w_d, double& white_d, double& resid_d) {
-#pragma clang fp contract(off)
-  const int lp = lane();
-  const int n = st.n;
-  double* v0 = L.vec;
-  double* v1 = L.vec + 64;
-  double* v2 = L.vec + 128;
-  double* v3 = L.vec + 192;
-  // gather the unflagged directions onto lanes p < n
-  if (lp < D) {
-    v0[lp] = phi_d;
-    v1[lp] = w_d;
-  }
-  lds_sync();
-  double phi_p = 0.0, w_p = 0.0;
-  if (lp < n) {
-    phi_p = v0[L.idx[lp]];
-    w_p = v1[L.idx[lp]];
-  }
-  lds_sync();
-  double rc, rs;
-  if (screen_type == SF_SCREEN_PHASE) {
-    double sn, cn;
-    sincos(phi_p, &sn, &cn);
-    rc = w_p * cn;   // W cos(phi)
-    rs = w_p * sn;   // W sin(phi)
-  } else {
-    rc = w_p * phi_p;
-    rs = 0.0;
-  }
-  if (lp < n) {
-    v0[lp] = rc;
-    v1[lp] = rs;
-    v2[lp] = w_p;
-  }
-  lds_sync();
-  // rr1 = U_k^T W r  (lane k < K);  G = U_k^T W U_k (row k)
-  double g1 = 0.0, g2 = 0.0;
-  if (lp < K) {
-    for (int p = 0; p < n; ++p) {
-      const double u = ucol(L, st, ld, p, lp);
-      g1 += u * v0[p];
-      g2 += u * v1[p];
-    }
-    for (int j = 0; j < K; ++j) {
-      double s = 0.0;
-      for (int p = 0; p < n; ++p)
-        s += ucol(L, st, ld, p, lp) * (v2[p] * ucol(L, st, ld, p, j));
-      L.M2[lp * ld + j] = s;
-    }
-  }
-  lds_sync();
-  // inv_u = pinv(G, atol=1e-3) applied to rr1.  lambda_min(G) >= min w over
-  // the unflagged rows (U_k has orthonormal columns over exactly those rows),
-  // so for wmin above the cutoff pinv == inverse: Cholesky.  Otherwise the
-  // eigen path reproduces the truncation.
-  double a1 = g1, a2 = g2;
-  if (K > 0) {
-    if (st.wmin > kPinvAtol * (1.0 + 1e-9)) {
-      wave_cholesky_solve2(L.M2, K, ld, a1, a2);
-    } else {
-      wave_jacobi(L.M2, L.M1, L.cs, L.pr, K, ld, kMaxSweeps);
-      if (lp < K) {
-        v0[lp] = g1;
-        v1[lp] = g2;
-      }
-      lds_sync();
-      double t1 = 0.0, t2 = 0.0;
-      if (lp < K) {
-        for (int q = 0; q < K; ++q) {
-          t1 += L.M1[q * ld + lp] * v0[q];
-          t2 += L.M1[q * ld + lp] * v1[q];
-        }
-        const double mu = L.M2[lp * ld + lp];
-        if (fabs(mu) > kPinvAtol) {
-          t1 /= mu;
-          t2 /= mu;
-        } else {
-          t1 = t2 = 0.0;
-        }
-      }
-      lds_sync();
-      if (lp < K) {
-        v2[lp] = t1;
-        v3[lp] = t2;
-      }
-      lds_sync();
-      a1 = a2 = 0.0;
-      if (lp < K)
-        for (int m = 0; m < K; ++m) {
-          a1 += L.M1[lp * ld + m] * v2[m];
-          a2 += L.M1[lp * ld + m] * v3[m];
-        }
-      lds_sync();
-    }
-  }
-  // h = U_k a  (lane p < n)
-  if (lp < K) {
-    v0[lp] = a1;
-    v1[lp] = a2;
-  }
-  lds_sync();
-  double h1 = 0.0, h2 = 0.0;
-  if (lp < n)
-    for (int k = 0; k < K; ++k) {
-      const double u = ucol(L, st, ld, lp, k);
-      h1 += u * v0[k];
-      h2 += u * v1[k];
-    }
-  lds_sync();
-  double screen;
-  if (n == 2 && K == 1) {
-    // two unflagged directions: the reference's U_k = e_2 (see fit_once in
-    // kl_fit_fast.hip); v0..v2 were overwritten above, so the second
-    // direction's terms are gathered again
-    if (lp < D) {
-      v0[lp] = phi_d;
-      v1[lp] = w_d;
-    }
-    lds_sync();
-    const double w2 = v1[L.idx[1]];
-    const double ph2 = v0[L.idx[1]];
-    lds_sync();
-    const double iw = w2 > kPinvAtol ? 1.0 / w2 : 0.0;
-    double t_re, t_im = 0.0;
-    if (screen_type == SF_SCREEN_PHASE) {
-      double sn, cn;
-      sincos(ph2, &sn, &cn);
-      t_re = iw * (w2 * cn);
-      t_im = iw * (w2 * sn);
-    } else {
-      t_re = iw * (w2 * ph2);
-    }
-    screen = lp != 1 ? 0.0 : screen_type == SF_SCREEN_PHASE ? atan2(t_im, t_re) : t_re;
-  } else if (screen_type == SF_SCREEN_PHASE) {
-    const double re = apply_pinv(L, st, ld, h1, v3);
-    const double im = apply_pinv(L, st, ld, h2, v3);
-    const double cre = apply_csub(L, n, ld, re, v3);
-    const double cim = apply_csub(L, n, ld, im, v3);
-    screen = atan2(cim, cre);
-  } else {
-    const double tf = apply_pinv(L, st, ld, h1, v3);
-    screen = apply_csub(L, n, ld, tf, v3);
-  }
-  const double white = apply_pinv(L, st, ld, screen, v3);
-  if (st.full) {
-    white_d = white;
-    const double cw = apply_csub(L, n, ld, white, v3);  // idx = identity
-    resid_d = phi_d - cw;
-    return;
-  }
-  // flagged directions: screen from the unflagged white coefficients, then
-  // re-whitened with the full pinv (stationscreen.py:565-582)
-  if (lp < n) {
-    v0[lp] = screen;
-    v1[lp] = white;
-  }
-  lds_sync();
-  const bool unfl = (lp < D) && (w_d > 0.0);
-  const uint64_t mask = __ballot(unfl);
-  double screen_all = 0.0;
-  if (lp < D) {
-    if (unfl) {
-      const int p = __builtin_amdgcn_mbcnt_hi((uint32_t)(mask >> 32),
-                                              __builtin_amdgcn_mbcnt_lo((uint32_t)mask, 0));
-      screen_all = v0[p];
-    } else {
-      for (int p = 0; p < n; ++p) screen_all += L.C[lp * ld + L.idx[p]] * v1[p];
-    }
-  }
-  lds_sync();
-  white_d = apply_pinv_full(L, D, ld, screen_all, v3);
-  resid_d = phi_d - screen_all;
 }
 
 __global__ __launch_bounds__(256) void kl_fit_general_kernel(
@@ -418,6 +160,8 @@ __global__ __launch_bounds__(256) void kl_fit_general_kernel(
   const int nwaves = blockDim.x / 64;
   const int wv = threadIdx.x / 64;
   const int d = lane();
+  using M = FitMath<false>;  // the transcendentals inlined
+  const Group<1> tm;
   FitLds L;
   L.C = smem;
   L.U = L.C + D * ld;
@@ -427,11 +171,12 @@ __global__ __launch_bounds__(256) void kl_fit_general_kernel(
   L.M1 = L.V + D * ld;
   L.M2 = L.M1 + D * ld;
   L.lam = L.M2 + D * ld;
-  L.vec = L.lam + 64;
-  L.idx = reinterpret_cast<int*>(L.vec + 6 * 64);
+  L.vecs = L.lam + 64;
+  L.idx = reinterpret_cast<int*>(L.vecs + 6 * 64);
   L.perm = L.idx + 64;
   L.cs = reinterpret_cast<double2*>(L.perm + 64);
   L.pr = reinterpret_cast<int2*>(L.cs + 64);
+  L.ld = ld;
   // shared basis -> LDS
   for (int e = threadIdx.x; e < D * D; e += blockDim.x) {
     const int r = e / D, c = e % D;
@@ -453,9 +198,7 @@ __global__ __launch_bounds__(256) void kl_fit_general_kernel(
     double phi_d = 0.0;
     float w_f = 0.0f;
     if (d < D) {
-      phi_d = phase[base + d];
-      if (refph) phi_d -= refph[(s / A) * D + d];
-      else if (ref >= 0) phi_d -= phase[base + (int64_t)(ref - a) * D + d];
+      phi_d = phase_ref(phase, refph, ref, s, a, A, D, d);
       w_f = weight[base + d];
     }
     const bool skipped = (ref_skip >= 0 && a == ref_skip) || skip[f * A + a];
@@ -472,38 +215,21 @@ __global__ __launch_bounds__(256) void kl_fit_general_kernel(
     double order = (double)st_order[a];
     const double station_order = order;
     double white_d = 0.0, resid_d = 0.0;
-    SubsetState st{-1, false, 0.0};
+    const bool live = d < D;
+    Subset st{-1, false, 0.0};
     bool mask_valid = false;
     for (int it = 0; it < niter; ++it) {
-      if (it > 0 && screen_type == SF_SCREEN_PHASE) {
-        // _flag_outliers on this slot (stationscreen.py:303-350): circular
-        // std across directions of the wrapped residual, flagged -> NaN
-        const bool live = d < D;
-        const bool any_unfl = __any(live && w_d > 0.0);
-        if (any_unfl) {
-          double r = fmod(resid_d, 2.0 * M_PI);
-          if (r < -M_PI) r += 2.0 * M_PI;
-          if (r > M_PI) r -= 2.0 * M_PI;
-          const bool inc = live && (w_d != 0.0) && !isnan(r);
-          double sn = 0.0, cn = 0.0;
-          if (inc) sincos(r, &sn, &cn);
-          const double cnt = wave_sum(inc ? 1.0 : 0.0);
-          const double ms = wave_sum(sn) / cnt;
-          const double mc = wave_sum(cn) / cnt;
-          const double stdv = sqrt(-2.0 * log(hypot(ms, mc)));
-          const bool outl = live && (fabs(r) > nsigma * stdv);
-          if (outl) w_d = 0.0;
-          if (__any(outl)) mask_valid = false;
-        }
+      if (it > 0 && screen_type == SF_SCREEN_PHASE && tm.any(live && w_d > 0.0)) {
+        if (tm.any(flag_circular_outliers<M>(tm, live, nsigma, resid_d, w_d)))
+          mask_valid = false;
       }
       const int norderiter = (adjust_order && it > 0) ? 4 : 1;
-      const uint64_t um = __ballot(d < D && w_d > 0.0);
+      const bool unfl = live && w_d > 0.0;
+      const uint64_t um = tm.ballot(unfl);
       const int n_unfl = __popcll(um);
       if (n_unfl == 0) continue;
       if (order > n_unfl - 1) order = n_unfl - 1;
-      bool hit_upper = false, hit_lower = false, hit_upper2 = false,
-           hit_lower2 = false;
-      double sign = 1.0, prev_redchi2 = 0.0;
+      OrderWalk walk;
       for (int oi = 0; oi < norderiter; ++oi) {
         bool skip_fit = false;
         if (it > 0) {
@@ -513,49 +239,21 @@ __global__ __launch_bounds__(256) void kl_fit_general_kernel(
         }
         if (!skip_fit) {
           if (!mask_valid) {
-            setup_subset(L, D, ld, w_d, st);
+            st.n = n_unfl;
+            st.full = n_unfl == D;
+            st.wmin = -tm.max(unfl ? -w_d : -INFINITY);
+            setup_subset(tm, L, D, st, um, unfl);
             mask_valid = true;
           }
-          fit_screen(L, st, D, ld, (int)order, screen_type, phi_d, w_d,
+          fit_screen(tm, L, st, D, (int)order, screen_type, um, phi_d, w_d,
                      white_d, resid_d);
         }
-        if (hit_lower2 || hit_upper2) break;
+        if (walk.done()) break;
         if (adjust_order && it > 0) {
-          double redchi2;
-          const bool unfl = d < D && w_d > 0.0;
-          if (screen_type == SF_SCREEN_PHASE) {
-            // _circ_chi2: squares of sin / cos (quirk Q7)
-            double sn = 0.0, cn = 0.0;
-            if (unfl) sincos(resid_d, &sn, &cn);
-            const double ww = unfl ? w_d : 0.0;
-            const double sw = wave_sum(ww);
-            const double m1 = wave_sum(sn * sn * ww) / sw;
-            const double m2 = wave_sum(cn * cn * ww) / sw;
-            redchi2 = (1.0 - hypot(m1, m2)) * sw / (n_unfl - order);
-          } else {
-            const double ww = unfl ? w_d : 0.0;
-            redchi2 = wave_sum(resid_d * resid_d * ww) / (n_unfl - order);
-          }
-          if (oi > 0) {
-            if (redchi2 > 1.0 && prev_redchi2 < redchi2) sign = -sign;
-            if (redchi2 < 1.0 && prev_redchi2 > redchi2) sign = -sign;
-          }
-          prev_redchi2 = redchi2;
-          const double order_factor = pow((double)n_unfl - order, 0.2);
-          double target = order - sign * order_factor * (1.0 - redchi2);
-          target = fmax(station_order, target);
-          target = fmin(rint(target), (double)(n_unfl - 1));
-          if (target <= 0.0) target = fmin(station_order, (double)(n_unfl - 1));
-          if (target == order) break;
-          if (target == n_unfl - 1) {
-            if (hit_upper) hit_upper2 = true;
-            hit_upper = true;
-          }
-          if (target == station_order) {
-            if (hit_lower) hit_lower2 = true;
-            hit_lower = true;
-          }
-          order = target;
+          // phase only: launch_fit rejects tec with niter > 1 on this path
+          const double redchi2 = slot_redchi2<M>(tm, screen_type, live, unfl, phi_d,
+                                                 w_d, resid_d, n_unfl, order);
+          if (walk.step<M>(oi, redchi2, n_unfl, station_order, order)) break;
         }
       }
     }

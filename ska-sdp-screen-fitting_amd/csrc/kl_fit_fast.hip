@@ -21,24 +21,24 @@
 //     keeps the reference's exact pinv semantics through a Jacobi solve.
 //
 // The outlier-flagging iterations become passes over all slots; between
-// passes the new masks are inserted, numbered and decomposed.
+// passes the new masks are inserted, numbered and decomposed.  The steps of a
+// slot that every fit kernel takes alike (referencing, chi^2, the order walk,
+// the outlier test, the two-direction rule, the truncated eigen-solve) are
+// in kl_fit_steps.h; fit_once, the mask table and the loads / stores are here.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 #include <cmath>
 #include <cstdlib>
 
+#include "kl_fit_steps.h"
 #include "sf_internal.h"
-#include "sf_wave.h"
 
 namespace sf {
 
-constexpr double kAtol = 1e-3;             // pinv(rcond=1e-3)
 constexpr size_t kLdsBytes = 160 * 1024;   // LDS of one gfx950 CU
-constexpr double kTinyW = 1e-3 * 1.001;    // slow-path threshold on weights
+constexpr double kTinyW = kPinvAtol * 1.001;  // slow-path threshold on weights
 constexpr unsigned long long kEmptyKey = 0ull;
-
-__host__ __device__ inline int ldo(int n) { return n | 1; }
 
 __device__ __forceinline__ unsigned long long mix64(unsigned long long x) {
   x ^= x >> 30;
@@ -78,16 +78,6 @@ __device__ int table_find(const unsigned long long* keys, int cap,
     h = (h + 1) & (cap - 1);
   }
   return -1;
-}
-
-__device__ __forceinline__ double phase_ref(const double* phase,
-                                            const double* refph, int sub,
-                                            int64_t s, int a, int A, int D,
-                                            int d) {
-  double v = phase[s * D + d];
-  if (refph) v -= refph[(s / A) * D + d];
-  else if (sub >= 0) v -= phase[(s + (sub - a)) * D + d];
-  return v;
 }
 
 // ---------------------------------------------------------------------------
@@ -195,7 +185,7 @@ __global__ __launch_bounds__(256) void kl_assign_kernel(
 //    global basis, kl_classify_kernel), so the LDS matrices are sized for
 //    D - 1 rows: at D = 50 a wave's 40,720 bytes let 4 waves share a CU's
 //    160 KiB (43,104 bytes, sized for D, let 3).
-__host__ __device__ inline int subset_ld(int D) { return ldo(D > 1 ? D - 1 : 1); }
+__host__ __device__ inline int subset_ld(int D) { return odd_ld(D > 1 ? D - 1 : 1); }
 __host__ __device__ inline int subset_rows(int D) { return D > 1 ? D - 1 : 1; }
 // NW: waves per mask of the subset Jacobi (wg_jacobi); the library runs 3
 // (kEigWavesDefault), SF_OPT_FIT_EIG_WAVES picks 1..4 -- the same bits at
@@ -240,9 +230,9 @@ __global__ __launch_bounds__(64 * NW) void kl_subset_eig_kernel(
       for (int q = 0; q < n; ++q) a[l * ld + q] = g_c[r * D + idx[q]];
     }
     __syncthreads();
-    wg_jacobi<NW>(a, v, cs, pr, n, ld, 40);
+    wg_jacobi<NW>(a, v, cs, pr, n, ld, kJacobiMaxSweeps);
     __syncthreads();
-    if (w0) wave_eig_order(a, n, ld, perm);
+    if (w0) eig_order(Group<1>{}, a, n, ld, perm);
     double* e = pool + (size_t)id * (D * D + D);
     if (w0 && l < n) {
       for (int r = 0; r < n; ++r) e[l * D + r] = v[l * ld + perm[r]];
@@ -295,7 +285,7 @@ __global__ __launch_bounds__(64) void kl_subset_secular_kernel(
     const int* __restrict__ ids, int table_cap, int level) {
 #pragma clang fp contract(off)
   extern __shared__ double smem[];
-  const int ld = D | 1;
+  const int ld = odd_ld(D);
   double* U = smem;            // [D][ld] current eigenvectors (row = direction)
   double* W = U + D * ld;      // [D][ld] w (row = non-deflated pole, col = root), then U w
   double* lam = W + D * ld;    // [64] current eigenvalues, ascending
@@ -597,7 +587,7 @@ __global__ __launch_bounds__(64) void kl_subset_secular_kernel(
       if (l == 0) status[id] = 1;
       continue;
     }
-    // ---- pool entry: columns by |mu| descending (wave_eig_order's rule)
+    // ---- pool entry: columns by |mu| descending (eig_order's rule)
     if (l < m) {
       const double v = fabs(lam[l]);
       int r2 = 0;
@@ -636,16 +626,19 @@ struct FastLds {
   double* vec;        // per wave [6][64]
   double2* cs;        // per wave [64]   (SLOW: Jacobi scratch)
   int2* pr;           // per wave [96]   (SLOW: Jacobi scratch)
+  __device__ void jacobi(double* a, double* v, int n, int ld) const {
+    wave_jacobi(a, v, cs, pr, n, ld, kJacobiMaxSweeps);
+  }
 };
 
 // U (and C, except in the one-slot pass, which reads C from L2: at D = 50
 // that halves the workgroup's shared LDS so 4 waves per SIMD fit) + lambda
 __host__ __device__ inline size_t fast_shared_bytes(int D, bool c_global) {
-  return (size_t)((c_global ? 1 : 2) * D * ldo(D) + 64) * sizeof(double);
+  return (size_t)((c_global ? 1 : 2) * D * odd_ld(D) + 64) * sizeof(double);
 }
 __host__ __device__ inline size_t fast_wave_bytes(int D, bool slow, bool lean = false) {
   if (lean) return (size_t)6 * 64 * sizeof(double);  // the vectors only
-  return (size_t)((slow ? 3 : 2) * D * ldo(D) + 64 + 6 * 64) * sizeof(double) +
+  return (size_t)((slow ? 3 : 2) * D * odd_ld(D) + 64 + 6 * 64) * sizeof(double) +
          (slow ? 64 * sizeof(double2) + 96 * sizeof(int2) : 0);
 }
 
@@ -656,49 +649,6 @@ struct Basis {
   const double* U;    // LDS (full basis, or a copied subset) or the global pool
   const double* lam;
 };
-
-// The fp64 transcendentals of the fit pass, inlined or called (NI).  Inlined
-// into the two-slots-per-wave pass, their polynomial constants were hoisted
-// out of the slot loop into ~100 VGPRs (235-256 VGPRs: 2 waves per SIMD for
-// a latency-bound kernel); called, that pass fits 128 VGPRs at 4 waves per
-// SIMD (config-4 fit 34 -> 28 ms, gain fits faster still).  The one-slot
-// pass (D > 32) calls them too, with C read from L2 so that its LDS admits
-// the same 4 waves per SIMD (calls alone, LDS-capped at 3, were slower).
-// The SLOW class keeps them inlined.  Same functions either way, same bits.
-__device__ __noinline__ void nl_sincos(double x, double* s, double* c) { sincos(x, s, c); }
-__device__ __noinline__ double nl_atan2(double y, double x) { return atan2(y, x); }
-__device__ __noinline__ double nl_log10(double x) { return log10(x); }
-__device__ __noinline__ double nl_pow(double x, double y) { return pow(x, y); }
-__device__ __noinline__ double nl_log(double x) { return log(x); }
-__device__ __noinline__ double nl_fmod(double x, double y) { return fmod(x, y); }
-
-template <bool NI>
-struct FitMath {
-  static __device__ __forceinline__ void sin_cos(double x, double* s, double* c) {
-    if constexpr (NI) nl_sincos(x, s, c); else sincos(x, s, c);
-  }
-  static __device__ __forceinline__ double arctan2(double y, double x) {
-    if constexpr (NI) return nl_atan2(y, x); else return atan2(y, x);
-  }
-  static __device__ __forceinline__ double lg10(double x) {
-    if constexpr (NI) return nl_log10(x); else return log10(x);
-  }
-  static __device__ __forceinline__ double power(double x, double y) {
-    if constexpr (NI) return nl_pow(x, y); else return pow(x, y);
-  }
-  static __device__ __forceinline__ double ln(double x) {
-    if constexpr (NI) return nl_log(x); else return log(x);
-  }
-  static __device__ __forceinline__ double mod(double x, double y) {
-    if constexpr (NI) return nl_fmod(x, y); else return fmod(x, y);
-  }
-};
-
-template <bool NI = false>
-__device__ __forceinline__ double model_value(int screen_type, double x) {
-  // amplitude screens are log10 values (stationscreen.py:535-548, 576-588)
-  return screen_type == SF_SCREEN_AMPLITUDE ? FitMath<NI>::power(10.0, x) : x;
-}
 
 // One _fit_screen (stationscreen.py:433-594) in the eigenbasis.  Lanes p < n
 // carry the unflagged directions (phi_p, w_p); returns, per DIRECTION lane d,
@@ -711,7 +661,6 @@ __device__ void fit_once(const FastLds& L, const Basis& B, int D, int ld,
 #pragma clang fp contract(off)
   using G = Group<SPW>;
   using M = FitMath<!SLOW>;
-  constexpr bool NI = !SLOW;
   // mat-vec loops: four terms' loads in flight, the sums still in order (the
   // same bits); the lean layout only (the general one would spill)
   constexpr int kMatVecUnroll = LEAN ? 4 : 1;
@@ -738,23 +687,7 @@ __device__ void fit_once(const FastLds& L, const Basis& B, int D, int ld,
     v2[l] = w_p;
   }
   lds_sync();
-  // Two unflagged directions (order clipped to n - 1 = 1): their C is
-  // [[0, b], [b, 0]], singular values |b| twice, and the reference's
-  // svd(C)[0] (LAPACK gesdd, stationscreen.py:427) is [[0, 1], [1, 0]] --
-  // unit vectors, not eigenvectors -- whose first column e_2 it keeps
-  // (:490-534): inv_u = pinv([w_2]) (0 below the 1e-3 cutoff), the fit
-  // C pinv(C) e_2 inv_u w_2 x_2 = (0, t), and the screen (0, atan2(t_im,
-  // t_re)) -- 0 = atan2(+0, +0) where the BLAS products leave +0
-  // (tests/golden/make_golden_ties.py pins it; LAPACK builds whose SVD
-  // leaves rounding residue there give atan2 of that residue instead)
-  const bool tie2 = n == 2 && K == 1;
-  double t_re = 0.0, t_im = 0.0;
-  if (tie2) {
-    const double w2 = v2[1];
-    const double iw = w2 > kAtol ? 1.0 / w2 : 0.0;
-    t_re = iw * v0[1];
-    t_im = iw * v1[1];
-  }
+  const Tie2 tie(n, K, v0, v1, v2);  // two unflagged directions: U_k = e_2
   double a1 = 0.0, a2 = 0.0;
   if (l < K) {
 #pragma unroll kMatVecUnroll
@@ -782,46 +715,14 @@ __device__ void fit_once(const FastLds& L, const Basis& B, int D, int ld,
       if (!SLOW) {
         wave_cholesky_solve2<SPW>(L.G, K, ld, a1, a2);
       } else {
-        // pinv(G, atol=1e-3) = sum_{|mu| > 1e-3} z z^T / mu (scipy >= 1.7)
-        wave_jacobi(L.G, L.M, L.cs, L.pr, K, ld, 40);
-        if (l < K) {
-          v0[l] = a1;
-          v1[l] = a2;
-        }
-        lds_sync();
-        double t1 = 0.0, t2 = 0.0;
-        if (l < K) {
-          for (int q = 0; q < K; ++q) {
-            t1 += L.M[q * ld + l] * v0[q];
-            t2 += L.M[q * ld + l] * v1[q];
-          }
-          const double mu = L.G[l * ld + l];
-          if (fabs(mu) > kAtol) {
-            t1 /= mu;
-            t2 /= mu;
-          } else {
-            t1 = t2 = 0.0;
-          }
-        }
-        lds_sync();
-        if (l < K) {
-          v2[l] = t1;
-          v3[l] = t2;
-        }
-        lds_sync();
-        a1 = a2 = 0.0;
-        if (l < K)
-          for (int m = 0; m < K; ++m) {
-            a1 += L.M[l * ld + m] * v2[m];
-            a2 += L.M[l * ld + m] * v3[m];
-          }
+        truncated_eig_solve(G{}, L, L.G, L.M, K, ld, v0, v1, v2, v3, a1, a2);
       }
     }
   }
   lds_sync();
   // C re = U_k m(a): keep the components whose eigenvalue survives the cutoff
   if (l < K) {
-    const bool keep = fabs(B.lam[l]) > kAtol;
+    const bool keep = fabs(B.lam[l]) > kPinvAtol;
     v0[l] = keep ? a1 : 0.0;
     v1[l] = keep ? a2 : 0.0;
   }
@@ -836,8 +737,7 @@ __device__ void fit_once(const FastLds& L, const Basis& B, int D, int ld,
       cim += u * v1[k];
     }
     screen = (screen_type == SF_SCREEN_PHASE) ? M::arctan2(cim, cre) : cre;
-    if (tie2)
-      screen = l != 1 ? 0.0 : (screen_type == SF_SCREEN_PHASE) ? M::arctan2(t_im, t_re) : t_re;
+    if (tie.on) screen = tie.template screen<M>(screen_type, l);
   }
   lds_sync();
   if (l < n) v2[l] = screen;
@@ -848,7 +748,7 @@ __device__ void fit_once(const FastLds& L, const Basis& B, int D, int ld,
 #pragma unroll kMatVecUnroll
     for (int p = 0; p < n; ++p) sh += B.U[p * B.ld + l] * v2[p];
     const double lm = B.lam[l];
-    const bool keep = fabs(lm) > kAtol;
+    const bool keep = fabs(lm) > kPinvAtol;
     v0[l] = keep ? sh / lm : 0.0;
     v1[l] = keep ? sh : 0.0;
   }
@@ -865,7 +765,7 @@ __device__ void fit_once(const FastLds& L, const Basis& B, int D, int ld,
   lds_sync();
   if (B.full) {
     white_d = white;
-    resid_d = phi_d - model_value<NI>(screen_type, cw);
+    resid_d = phi_d - model_value<M>(screen_type, cw);
     return;
   }
   // flagged directions (stationscreen.py:565-582): screen from the subset's
@@ -902,7 +802,7 @@ __device__ void fit_once(const FastLds& L, const Basis& B, int D, int ld,
 #pragma unroll kMatVecUnroll
     for (int p = 0; p < D; ++p) sh += L.U[p * ld + l] * v2[p];
     const double lm = L.lam[l];
-    v0[l] = fabs(lm) > kAtol ? sh / lm : 0.0;
+    v0[l] = fabs(lm) > kPinvAtol ? sh / lm : 0.0;
   }
   lds_sync();
   double wa = 0.0;
@@ -911,17 +811,7 @@ __device__ void fit_once(const FastLds& L, const Basis& B, int D, int ld,
     for (int r = 0; r < D; ++r) wa += L.U[l * ld + r] * v0[r];
   lds_sync();
   white_d = wa;
-  resid_d = phi_d - model_value<NI>(screen_type, sall);
-}
-
-// residual as the outlier test / chi^2 see it (stationscreen.py:660-668,
-// 733-746): phase & tec use the residual, amplitude the log10 ratio
-template <bool NI = false>
-__device__ __forceinline__ double screen_diff(int screen_type, double val,
-                                              double resid) {
-  if (screen_type == SF_SCREEN_AMPLITUDE)
-    return FitMath<NI>::lg10(val) - FitMath<NI>::lg10(fabs(val - resid));
-  return resid;
+  resid_d = phi_d - model_value<M>(screen_type, sall);
 }
 
 // LEAN (fast class, every slot's unflagged weights equal -- the 0/1 weights
@@ -946,10 +836,10 @@ __global__ __launch_bounds__(256, SLOW ? 1 : SF_FIT_MINW) void kl_fit_pass_kerne
     int32_t* __restrict__ order_out) {
 #pragma clang fp contract(off)
   extern __shared__ double smem[];
-  const int ld = ldo(D);
+  const int ld = odd_ld(D);
   using G = Group<SPW>;
   using M = FitMath<!SLOW>;
-  constexpr bool NI = !SLOW;
+  const G tm;
   constexpr bool CG = SPW == 1;  // C read from global (L2), not LDS
   const int nwaves = blockDim.x / 64;
   const int nslots = nwaves * SPW;                  // slots in flight per WG
@@ -1077,53 +967,16 @@ __global__ __launch_bounds__(256, SLOW ? 1 : SF_FIT_MINW) void kl_fit_pass_kerne
         fit_once<SLOW, SPW, LEAN>(L, B, D, ld, (int)order, screen_type, uniform, wmin,
                        phi_p, w_p, phi_d, w_d, white_d, resid_d);
       } else if (adjust_order) {
-        bool hit_upper = false, hit_lower = false, hit_upper2 = false,
-             hit_lower2 = false;
-        double sign = 1.0, prev_redchi2 = 0.0;
+        OrderWalk walk;
         for (int oi = 0; oi < 4; ++oi) {
           // oi == 0: the weights always compare equal (quirk Q2) -> no fit
           if (oi > 0)
             fit_once<SLOW, SPW, LEAN>(L, B, D, ld, (int)order, screen_type, uniform, wmin,
                            phi_p, w_p, phi_d, w_d, white_d, resid_d);
-          if (hit_lower2 || hit_upper2) break;
-          double redchi2;
-          if (screen_type == SF_SCREEN_PHASE) {
-            double sn = 0.0, cn = 0.0;
-            if (unfl) M::sin_cos(resid_d, &sn, &cn);
-            const double ww = unfl ? w_d : 0.0;
-            const double sw = G::sum(ww);
-            const double m1 = G::sum(sn * sn * ww) / sw;
-            const double m2 = G::sum(cn * cn * ww) / sw;
-            redchi2 = (1.0 - hypot(m1, m2)) * sw / (n_unfl - order);
-          } else {
-            // np.sum(square(diff) * w) over all directions
-            double t = 0.0;
-            if (d < D) {
-              const double sd = screen_diff<NI>(screen_type, phi_d, resid_d);
-              t = (sd * sd) * w_d;
-            }
-            redchi2 = G::sum(t) / (n_unfl - order);
-          }
-          if (oi > 0) {
-            if (redchi2 > 1.0 && prev_redchi2 < redchi2) sign = -sign;
-            if (redchi2 < 1.0 && prev_redchi2 > redchi2) sign = -sign;
-          }
-          prev_redchi2 = redchi2;
-          const double order_factor = M::power((double)n_unfl - order, 0.2);
-          double target = order - sign * order_factor * (1.0 - redchi2);
-          target = fmax(station_order, target);
-          target = fmin(rint(target), (double)(n_unfl - 1));
-          if (target <= 0.0) target = fmin(station_order, (double)(n_unfl - 1));
-          if (target == order) break;
-          if (target == n_unfl - 1) {
-            if (hit_upper) hit_upper2 = true;
-            hit_upper = true;
-          }
-          if (target == station_order) {
-            if (hit_lower) hit_lower2 = true;
-            hit_lower = true;
-          }
-          order = target;
+          if (walk.done()) break;
+          const double redchi2 = slot_redchi2<M>(tm, screen_type, d < D, unfl, phi_d,
+                                                 w_d, resid_d, n_unfl, order);
+          if (walk.template step<M>(oi, redchi2, n_unfl, station_order, order)) break;
         }
       }
     }
@@ -1132,23 +985,10 @@ __global__ __launch_bounds__(256, SLOW ? 1 : SF_FIT_MINW) void kl_fit_pass_kerne
     // tec / amplitude: one sigma per station block -> kl_block_sigma/flag
     if (it + 1 < niter && screen_type == SF_SCREEN_PHASE) {
       const bool live = d < D;
-      if (G::any(live && w_d > 0.0)) {
-        double r = M::mod(resid_d, 2.0 * M_PI);
-        if (r < -M_PI) r += 2.0 * M_PI;
-        if (r > M_PI) r -= 2.0 * M_PI;
-        const bool inc = live && (w_d != 0.0) && !isnan(r);
-        double sn = 0.0, cn = 0.0;
-        if (inc) M::sin_cos(r, &sn, &cn);
-        const double cnt = G::sum(inc ? 1.0 : 0.0);
-        const double ms = G::sum(sn) / cnt;
-        const double mc = G::sum(cn) / cnt;
-        const double stdv = sqrt(-2.0 * M::ln(hypot(ms, mc)));
-        const bool outl = live && (fabs(r) > nsigma * stdv);
-        if (outl) w_d = 0.0;
-        if (G::any(outl)) {
-          const unsigned long long nm = G::ballot(live && w_d > 0.0);
-          if (d == 0) pos[s] = (nm == 0ull) ? -2 : table_insert(keys, cap, nm);
-        }
+      if (G::any(live && w_d > 0.0) &&
+          G::any(flag_circular_outliers<M>(tm, live, nsigma, resid_d, w_d))) {
+        const unsigned long long nm = G::ballot(live && w_d > 0.0);
+        if (d == 0) pos[s] = (nm == 0ull) ? -2 : table_insert(keys, cap, nm);
       }
     }
     if (d < D) {
@@ -1244,12 +1084,6 @@ size_t next_pow2(size_t x) {
 
 }  // namespace
 
-#define SF_TRYF(x)                 \
-  do {                             \
-    int rc_ = (x);                 \
-    if (rc_ != SF_OK) return rc_;  \
-  } while (0)
-
 static int ensure_pool(sf_ctx* ctx, size_t need) {
   const size_t entry = (size_t)ctx->D * ctx->D + ctx->D;
   if (ctx->pool_D != ctx->D) {
@@ -1264,8 +1098,8 @@ static int ensure_pool(sf_ctx* ctx, size_t need) {
   size_t cap = ctx->pool_cap ? ctx->pool_cap : 1024;
   while (cap < need) cap *= 2;
   size_t pc = ctx->pool_cap * entry, mc = ctx->pool_cap;
-  SF_TRYF(grow(&ctx->d_pool, pc, cap * entry, true));
-  SF_TRYF(grow(&ctx->d_pool_mask, mc, cap, true));
+  SF_TRY_RC(grow(&ctx->d_pool, pc, cap * entry, true));
+  SF_TRY_RC(grow(&ctx->d_pool_mask, mc, cap, true));
   ctx->pool_cap = cap;
   return SF_OK;
 }
@@ -1301,7 +1135,7 @@ static int number_and_decompose(sf_ctx* ctx, int* n_slow, int* n_nonuniform) {
   *n_slow = cnt[2];
   *n_nonuniform = cnt[4];
   if (cnt[0] > old_cap) {
-    SF_TRYF(ensure_pool(ctx, (size_t)cnt[0]));
+    SF_TRY_RC(ensure_pool(ctx, (size_t)cnt[0]));
     hipLaunchKernelGGL(kl_fill_mask_kernel, dim3((cap + 255) / 256), dim3(256),
                        0, ctx->stream, ctx->d_keys, ctx->d_ids, cap,
                        ctx->d_pool_mask, old_cap);
@@ -1315,10 +1149,10 @@ static int number_and_decompose(sf_ctx* ctx, int* n_slow, int* n_nonuniform) {
     // (the status of every pool entry of the call is kept: a later pass's
     // masks take an earlier pass's entries as ancestors only if the chain
     // built them; the stream was synchronised above, so the copy is safe)
-    SF_TRYF(grow(&ctx->d_pool_status, ctx->pool_status_cap, ctx->pool_cap, true));
+    SF_TRY_RC(grow(&ctx->d_pool_status, ctx->pool_status_cap, ctx->pool_cap, true));
     SF_HIP(hipMemsetAsync(ctx->d_pool_status + cnt[1], 1, (size_t)n_new, ctx->stream));
     const int D = ctx->D;
-    const int ldd = D | 1;
+    const int ldd = odd_ld(D);
     const size_t shm = (size_t)2 * D * ldd * sizeof(double) + 6 * 64 * sizeof(double) +
                        4 * 64 * sizeof(int);
     if (shm > 64 * 1024)
@@ -1448,6 +1282,29 @@ int launch_block_sigma(sf_ctx* ctx, int T, int F, int A, const double* phase,
   return SF_OK;
 }
 
+// What every fit launcher needs beside its own tables: the block sigma, the
+// counters, and scratch for the outputs the caller does not want (they carry
+// the state from pass to pass).
+int fit_buffers(sf_ctx* ctx, int64_t S, int F, int A, double** resid,
+                float** w_out, int32_t** order_out) {
+  const size_t n = (size_t)S * ctx->D;
+  if (!*resid) {
+    SF_TRY_RC(grow(&ctx->d_scratch, ctx->scratch_cap, n));
+    *resid = ctx->d_scratch;
+  }
+  if (!*w_out) {
+    SF_TRY_RC(grow(&ctx->d_wscratch, ctx->wscratch_cap, n));
+    *w_out = ctx->d_wscratch;
+  }
+  if (!*order_out) {
+    SF_TRY_RC(grow(&ctx->d_oscratch, ctx->oscratch_cap, (size_t)S));
+    *order_out = ctx->d_oscratch;
+  }
+  SF_TRY_RC(grow(&ctx->d_sigma, ctx->sigma_cap, (size_t)F * A));
+  SF_TRY_RC(grow(&ctx->d_counters, ctx->counters_cap, 8));
+  return SF_OK;
+}
+
 int launch_fit(sf_ctx* ctx, const double* phase, const float* weight, int T,
                int F, int A, const sf_fit_params* p, double* coef,
                double* resid, float* w_out, int32_t* order_out) {
@@ -1457,7 +1314,7 @@ int launch_fit(sf_ctx* ctx, const double* phase, const float* weight, int T,
   const int D = ctx->D;
   const int64_t S = (int64_t)T * F * A;
   const RefSpec r = ref_spec(p, A);
-  SF_TRYF(launch_skip(ctx, phase, weight, T, F, A, r));
+  SF_TRY_RC(launch_skip(ctx, phase, weight, T, F, A, r));
 
   static const char* env = std::getenv("SCREENFIT_FIT");
   if (ctx->force_general || (env && env[0] == 'g')) {
@@ -1469,38 +1326,16 @@ int launch_fit(sf_ctx* ctx, const double* phase, const float* weight, int T,
     return launch_fit_general(ctx, nullptr, nullptr, S, phase, weight, T, F, A,
                               p, r, coef, resid, w_out, order_out);
   }
-  // scratch for outputs the caller does not want (they carry pass state)
-  if (!resid) {
-    SF_TRYF(grow(&ctx->d_scratch, ctx->scratch_cap, (size_t)S * D));
-    resid = ctx->d_scratch;
-  }
-  if (!w_out || !order_out) {
-    size_t wc = 0, oc = 0;
-    if (ctx->d_wscratch) (void)hipFree(ctx->d_wscratch);
-    if (ctx->d_oscratch) (void)hipFree(ctx->d_oscratch);
-    ctx->d_wscratch = nullptr;
-    ctx->d_oscratch = nullptr;
-    SF_TRYF(grow(&ctx->d_wscratch, wc, (size_t)S * D));
-    SF_TRYF(grow(&ctx->d_oscratch, oc, (size_t)S));
-    if (!w_out) w_out = ctx->d_wscratch;
-    if (!order_out) order_out = ctx->d_oscratch;
-  }
+  SF_TRY_RC(fit_buffers(ctx, S, F, A, &resid, &w_out, &order_out));
   if (ctx->slot_cap < (size_t)S) {
     size_t c1 = 0, c3 = 0;
     if (ctx->d_pos) (void)hipFree(ctx->d_pos);
     if (ctx->d_class) (void)hipFree(ctx->d_class);
     ctx->d_pos = nullptr;
     ctx->d_class = nullptr;
-    SF_TRYF(grow(&ctx->d_pos, c1, (size_t)S));
-    SF_TRYF(grow(&ctx->d_class, c3, (size_t)S));
+    SF_TRY_RC(grow(&ctx->d_pos, c1, (size_t)S));
+    SF_TRY_RC(grow(&ctx->d_class, c3, (size_t)S));
     ctx->slot_cap = (size_t)S;
-  }
-  if (ctx->sigma_cap < (size_t)F * A) {
-    size_t c = 0;
-    if (ctx->d_sigma) (void)hipFree(ctx->d_sigma);
-    ctx->d_sigma = nullptr;
-    SF_TRYF(grow(&ctx->d_sigma, c, (size_t)F * A));
-    ctx->sigma_cap = (size_t)F * A;
   }
   // every pass inserts at most one mask per slot
   const size_t tcap = next_pow2((size_t)(2 * p->niter + 2) * (size_t)S + 64);
@@ -1510,15 +1345,11 @@ int launch_fit(sf_ctx* ctx, const double* phase, const float* weight, int T,
     if (ctx->d_ids) (void)hipFree(ctx->d_ids);
     ctx->d_keys = nullptr;
     ctx->d_ids = nullptr;
-    SF_TRYF(grow(&ctx->d_keys, c1, tcap));
-    SF_TRYF(grow(&ctx->d_ids, c2, tcap));
+    SF_TRY_RC(grow(&ctx->d_keys, c1, tcap));
+    SF_TRY_RC(grow(&ctx->d_ids, c2, tcap));
     ctx->table_cap = tcap;
   }
-  if (!ctx->d_counters) {
-    size_t c = 0;
-    SF_TRYF(grow(&ctx->d_counters, c, 8));
-  }
-  SF_TRYF(ensure_pool(ctx, 1024));
+  SF_TRY_RC(ensure_pool(ctx, 1024));
   const int cap = (int)ctx->table_cap;
   SF_HIP(hipMemsetAsync(ctx->d_keys, 0, ctx->table_cap * sizeof(unsigned long long),
                         ctx->stream));
@@ -1548,14 +1379,14 @@ int launch_fit(sf_ctx* ctx, const double* phase, const float* weight, int T,
   const bool block_flags = p->screen_type != SF_SCREEN_PHASE;
   for (int it = 0; it < p->niter; ++it) {
     int n_slow = 0, n_nonuniform = 0;
-    SF_TRYF(number_and_decompose(ctx, &n_slow, &n_nonuniform));
-    SF_TRYF(launch_pass<false>(ctx, it, p, r, S, F, A, phase, coef, resid,
+    SF_TRY_RC(number_and_decompose(ctx, &n_slow, &n_nonuniform));
+    SF_TRY_RC(launch_pass<false>(ctx, it, p, r, S, F, A, phase, coef, resid,
                                w_out, order_out, n_nonuniform == 0));
     if (n_slow > 0)
-      SF_TRYF(launch_pass<true>(ctx, it, p, r, S, F, A, phase, coef, resid,
+      SF_TRY_RC(launch_pass<true>(ctx, it, p, r, S, F, A, phase, coef, resid,
                                 w_out, order_out, false));
     if (block_flags && it + 1 < p->niter) {
-      SF_TRYF(launch_block_sigma(ctx, T, F, A, phase, r, p->screen_type, resid,
+      SF_TRY_RC(launch_block_sigma(ctx, T, F, A, phase, r, p->screen_type, resid,
                                  w_out));
       hipLaunchKernelGGL(kl_block_flag_kernel, dim3((unsigned)((S + 255) / 256)),
                          dim3(256), 0, ctx->stream, S, F, A, D, phase, r.refph,

@@ -1,6 +1,7 @@
 // kl_fit_wide.h -- workgroup-level (256-thread) float64 building blocks of the
-// KL fit with 61..128 directions (kl_fit_wide.hip): reductions and votes over
-// up to 128 rows, the cyclic Jacobi eigen-solver and a Cholesky solver.
+// KL fit with 61..128 directions: reductions and votes over up to 128 rows
+// (WideTeam: the Team of kl_fit_steps.h), the cyclic Jacobi eigen-solver on
+// the rotation of sf_wave.h, and a Cholesky solver.
 //
 // Layout convention: thread t of the workgroup owns row i = t & 127 and
 // belongs to column share w = t >> 7 (two shares).  Per-row values are held
@@ -22,10 +23,6 @@ constexpr int kWideRows = 128;    // rows (directions): one thread each
 constexpr int kWideShares = 2;    // column shares of the Jacobi rounds
 constexpr int kWideThreads = kWideRows * kWideShares;
 constexpr int kWideCH = 8;        // column pairs per Jacobi chunk
-constexpr int kWideMaxSweeps = 40;
-constexpr double kWideAtol = 1e-3;  // pinv(rcond=1e-3), scipy>=1.7 semantics
-
-__host__ __device__ inline int wide_ld(int n) { return n | 1; }
 
 // Vectors and Jacobi scratch of one workgroup (LDS).
 struct WideSmall {
@@ -93,13 +90,38 @@ __device__ __forceinline__ int wide_rank(const WideMask& m, int i) {
   return __popcll(m.lo) + __popcll(m.hi & ((1ull << (i - 64)) - 1ull));
 }
 
-// wg_jacobi (sf_wave.h) for n <= 128 on 256 threads: the same round-robin
-// pairing, the same rotation formulas and the same `off > 1e-26 (off + dia)`
-// test, followed by one polishing sweep (below).  Thread t owns row t & 127
-// and updates the column pairs of share t >> 7.  A row's partner row may belong to another wave, so a workgroup
-// barrier separates a chunk's reads from its writes (the chunks of a round
-// touch disjoint columns: one barrier per chunk is enough), and every thread
-// runs the same number of chunks whatever its share holds.  n >= 1.
+// The Team of the slot steps (kl_fit_steps.h) on the workgroup: lane = thread
+// (threads < n hold the gathered rows), row / share as above, one barrier
+// pair per sum / max / ballot.
+struct WideTeam {
+  using Mask = WideMask;
+  double* red;              // WideSmall::red
+  unsigned long long* bal;  // WideSmall::bal
+  __device__ static int lane() { return threadIdx.x; }
+  __device__ static int row() { return wide_row(); }
+  __device__ static int share() { return wide_share(); }
+  __device__ static constexpr int shares() { return kWideShares; }
+  __device__ static void sync() { __syncthreads(); }
+  template <int N>
+  __device__ void sum(double (&x)[N]) const { wide_sum(x, red); }
+  __device__ double max(double x) const { return wide_max(x, red); }
+  __device__ Mask ballot(bool x) const { return wide_ballot(x, bal); }
+  // set bits of m below this thread's row (threads < 128)
+  __device__ static int rank(const Mask& m) { return wide_rank(m, threadIdx.x); }
+};
+
+// wg_jacobi for n <= 128 on 256 threads: the same round-robin pairing, the
+// same rotations (jacobi_pair) and the same `off > 1e-26 (off + dia)` test,
+// followed by one polishing sweep (below).  Thread t owns row t & 127 and
+// updates the column pairs of share t >> 7.  A row's partner row may belong
+// to another wave, so a workgroup barrier separates a chunk's reads from its
+// writes (the chunks of a round touch disjoint columns: one barrier per chunk
+// is enough), and every thread runs the same number of chunks whatever its
+// share holds.  n >= 1.
+// The chunk update is spelled out here, not through jacobi_update_read /
+// _write: the same arithmetic through the helpers was scheduled differently
+// (3 more s_waitcnt in this function) and the D = 80 fit ran 1.4 % slower,
+// beyond the parent's spread.
 __device__ inline int wide_jacobi(double* a, double* v, WideSmall& S, int n,
                                   int ld, int max_sweeps) {
 #pragma clang fp contract(off)
@@ -138,46 +160,7 @@ __device__ inline int wide_jacobi(double* a, double* v, WideSmall& S, int n,
       polished = true;
     }
     for (int r = 0; r < m - 1; ++r) {
-      // pair k of round r: (m-1, r) for k = 0, else (r+k, r-k) mod (m-1);
-      // a pair with the dummy player n (n odd) becomes (j, j)
-      if (t < npairs) {
-        int p, q;
-        if (t == 0) {
-          p = r;
-          q = m - 1;
-        } else {
-          p = r + t;
-          if (p >= m - 1) p -= m - 1;
-          q = r - t;
-          if (q < 0) q += m - 1;
-        }
-        if (q >= n) q = p;
-        if (p >= n) p = q;
-        if (p > q) { const int x = p; p = q; q = x; }
-        double c = 1.0, s = 0.0;
-        const double apq = a[p * ld + q];
-        if (p != q && apq != 0.0) {
-          const double app = a[p * ld + p];
-          const double aqq = a[q * ld + q];
-          const double tau = (aqq - app) / (2.0 * apq);
-          double tt;
-          if (fabs(tau) > 1e150) {
-            tt = 0.5 / tau;
-          } else {
-            tt = 1.0 / (fabs(tau) + sqrt(1.0 + tau * tau));
-            if (tau < 0.0) tt = -tt;
-          }
-          c = 1.0 / sqrt(1.0 + tt * tt);
-          s = tt * c;
-        }
-        S.pr[t] = make_int2(p, q);
-        S.cs[p] = make_double2(c, -s);  // row/col p: x_p' = c x_p - s x_q
-        S.part[p] = q;
-        if (q != p) {
-          S.cs[q] = make_double2(c, s);  // row/col q: x_q' = c x_q + s x_p
-          S.part[q] = p;
-        }
-      }
+      if (t < npairs) jacobi_pair(a, ld, t, r, m, n, S.cs, S.pr, S.part);
       __syncthreads();
       const double2 ri = own ? S.cs[i] : make_double2(1.0, 0.0);
       const int pir = own ? S.part[i] : 0;
@@ -231,22 +214,6 @@ __device__ inline int wide_jacobi(double* a, double* v, WideSmall& S, int n,
     }
   }
   return sweep;
-}
-
-// perm[rank] = i by descending |lambda_i| (ties by index): the column order
-// of U from svd() of a symmetric matrix.
-__device__ inline void wide_eig_order(const double* a, int n, int ld, int* perm) {
-  const int t = threadIdx.x;
-  if (t < n) {
-    const double li = fabs(a[t * ld + t]);
-    int rank = 0;
-    for (int j = 0; j < n; ++j) {
-      const double lj = fabs(a[j * ld + j]);
-      rank += (lj > li) || (lj == li && j < t);
-    }
-    perm[rank] = t;
-  }
-  __syncthreads();
 }
 
 // In-place Cholesky G = L L^T of the SPD k x k matrix g (lower triangle

@@ -88,13 +88,9 @@ struct sf_ctx {
   double* d_u = nullptr;       // [D][D] (columns sorted by |lambda| desc)
   double* d_eig = nullptr;     // [D]    (signed eigenvalues, sorted)
   // wide fit (kl_fit_wide.hip): the matrices of the basis kernel, then of the
-  // fit workgroups that do not fit the LDS; state when the caller passes NULL
+  // fit workgroups that do not fit the LDS
   double* d_wide_ws = nullptr;
   size_t wide_ws_cap = 0;      // doubles
-  float* d_wide_w = nullptr;
-  size_t wide_w_cap = 0;
-  int32_t* d_wide_o = nullptr;
-  size_t wide_o_cap = 0;
   // pixel grid (sf_set_grid)
   int nx = 0, ny = 0;
   int64_t n_pix = 0;
@@ -150,10 +146,13 @@ struct sf_ctx {
   size_t slot_cap = 0;
   int* d_counters = nullptr;  // [0] ids, [1] range start, [2] slow, [3] error,
                               // [4] non-uniform-weight slots
+  size_t counters_cap = 0;
   double* d_scratch = nullptr;           // resid / state when caller passes NULL
   size_t scratch_cap = 0;
-  float* d_wscratch = nullptr;
+  float* d_wscratch = nullptr;           // w_out / order_out likewise
+  size_t wscratch_cap = 0;
   int32_t* d_oscratch = nullptr;
+  size_t oscratch_cap = 0;
   // Gaussian weights of sf_tess_fill / sf_smooth, pass buffer of sf_smooth
   double* d_gw = nullptr;
   size_t gw_cap = 0;                     // doubles
@@ -216,6 +215,10 @@ int launch_basis(sf_ctx* ctx);
 int launch_block_sigma(sf_ctx* ctx, int T, int F, int A, const double* phase,
                        const RefSpec& r, int screen_type, const double* resid,
                        const float* w_out);
+// block sigma, counters and scratch for NULL outputs of a fit of S slots
+// (kl_fit_fast.hip; every fit launcher)
+int fit_buffers(sf_ctx* ctx, int64_t S, int F, int A, double** resid,
+                float** w_out, int32_t** order_out);
 // 60 < D <= SF_MAX_FIT_DIR: kl_fit_wide.hip
 int launch_basis_wide(sf_ctx* ctx);
 int launch_fit_wide(sf_ctx* ctx, const double* phase, const float* weight,

@@ -1,5 +1,8 @@
 // sf_wave.h -- wavefront-level (64-lane) float64 building blocks for the KL
 // fit: reductions, a symmetric Jacobi eigen-solver and a Cholesky solver.
+// The Jacobi's rotation of a pair and update of a column pair (jacobi_pair,
+// jacobi_update_read / _write) serve the sweep loops: wave_jacobi and
+// wg_jacobi here; wide_jacobi of the 256-thread fit takes the rotation.
 //
 // Layout convention: an n x n matrix (n <= 64) lives in LDS with row stride
 // `ld` (odd, so that lane i reading row i with ds_read_b64 hits 32 distinct
@@ -41,16 +44,29 @@ __device__ __forceinline__ double bcast(double v, int src) {
 // Every reduction / vote / broadcast stays inside the group, and with
 // SPW = 1 each is the exact 64-lane operation above (same order of adds),
 // so packing slots changes no result bit.
+// It is the Team of a wave or half-wave for the slot steps (kl_fit_steps.h):
+// one lane per row, no column shares, LDS ordered by lds_sync.
 template <int SPW>
 struct Group {
   static constexpr int kWidth = 64 / SPW;
+  using Mask = unsigned long long;
   __device__ static int lane() { return __lane_id() & (kWidth - 1); }
+  __device__ static int row() { return lane(); }
+  __device__ static constexpr int share() { return 0; }
+  __device__ static constexpr int shares() { return 1; }
+  __device__ static void sync() { lds_sync(); }
   __device__ static int first() { return __lane_id() & ~(kWidth - 1); }
   __device__ static int index() { return __lane_id() / kWidth; }
   __device__ static double sum(double v) {
 #pragma unroll
     for (int o = kWidth / 2; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
     return v;
+  }
+  // N sums at once, each the butterfly above
+  template <int N>
+  __device__ static void sum(double (&x)[N]) {
+#pragma unroll
+    for (int k = 0; k < N; ++k) x[k] = sum(x[k]);
   }
   __device__ static double max(double v) {
 #pragma unroll
@@ -88,6 +104,94 @@ __device__ __forceinline__ int rr_partner(int i, int r, int m) {
   if (p < 0) p += mm;
   if (p >= mm) p -= mm;
   return p;
+}
+
+// Rotation `t` of round r of the cyclic Jacobi below (one lane or thread per
+// pair; m = n + (n & 1) players): pair t is (m-1, r) for t = 0, else
+// (r+t, r-t) mod (m-1); a pair with the dummy player n (n odd) becomes
+// (j, j) under the identity rotation.  Writes the pair to pr[t], the
+// rotation of its two rows / columns to cs and each one's partner to part.
+__device__ __forceinline__ void jacobi_pair(const double* a, int ld, int t,
+                                            int r, int m, int n, double2* cs,
+                                            int2* pr, int* part) {
+#pragma clang fp contract(off)
+  int p, q;
+  if (t == 0) {
+    p = r;
+    q = m - 1;
+  } else {
+    p = r + t;
+    if (p >= m - 1) p -= m - 1;
+    q = r - t;
+    if (q < 0) q += m - 1;
+  }
+  if (q >= n) q = p;
+  if (p >= n) p = q;
+  if (p > q) { const int x = p; p = q; q = x; }
+  double c = 1.0, s = 0.0;
+  const double apq = a[p * ld + q];
+  if (p != q && apq != 0.0) {
+    const double app = a[p * ld + p];
+    const double aqq = a[q * ld + q];
+    const double tau = (aqq - app) / (2.0 * apq);
+    double tt;
+    if (fabs(tau) > 1e150) {
+      tt = 0.5 / tau;
+    } else {
+      tt = 1.0 / (fabs(tau) + sqrt(1.0 + tau * tau));
+      if (tau < 0.0) tt = -tt;
+    }
+    c = 1.0 / sqrt(1.0 + tt * tt);
+    s = tt * c;
+  }
+  pr[t] = make_int2(p, q);
+  cs[p] = make_double2(c, -s);  // row/col p: x_p' = c x_p - s x_q
+  part[p] = q;
+  if (q != p) {
+    cs[q] = make_double2(c, s);  // row/col q: x_q' = c x_q + s x_p
+    part[q] = p;
+  }
+}
+
+// The update of one column pair jq = (j, pj) of a round, A <- J^T A J,
+// V <- V J, for the row `row` with partner row `pir` and row rotation ri:
+// the read half computes the row's new elements of columns j (na, nv) and
+// pj (nb, nw); the caller orders every read of a chunk of pairs before the
+// write half (lds_sync or a barrier).  An unpaired column is paired with
+// itself under the identity rotation, so a chunk's reads are branch-free and
+// issue back-to-back.
+__device__ __forceinline__ void jacobi_update_read(
+    const double* a, const double* v, int ld, int row, int pir, double2 ri,
+    int2 jq, const double2* cs, double& na, double& nb, double& nv, double& nw) {
+#pragma clang fp contract(off)
+  const int j = jq.x, pj = jq.y;
+  const double2 rj = cs[j];
+  const double2 rq = cs[pj];
+  const double aij = a[row * ld + j];
+  const double aiq = a[row * ld + pj];
+  const double apj = a[pir * ld + j];
+  const double apq = a[pir * ld + pj];
+  const double vij = v[row * ld + j];
+  const double viq = v[row * ld + pj];
+  // row rotation then column rotation, summed symmetrically
+  const double r_j = ri.x * aij + ri.y * apj;   // R_ij
+  const double r_q = ri.x * aiq + ri.y * apq;   // R_i,pj
+  na = rj.x * r_j + rj.y * r_q;                 // A''_ij
+  nb = rq.x * r_q + rq.y * r_j;                 // A''_i,pj
+  nv = rj.x * vij + rj.y * viq;
+  nw = rq.x * viq + rq.y * vij;
+}
+
+__device__ __forceinline__ void jacobi_update_write(double* a, double* v, int ld,
+                                                    int i, int2 jq, double na,
+                                                    double nb, double nv,
+                                                    double nw) {
+  a[i * ld + jq.x] = na;
+  v[i * ld + jq.x] = nv;
+  if (jq.y != jq.x) {
+    a[i * ld + jq.y] = nb;
+    v[i * ld + jq.y] = nw;
+  }
 }
 
 // Cyclic Jacobi eigen-decomposition of the symmetric n x n matrix `a`
@@ -129,45 +233,8 @@ __device__ inline int wave_jacobi(double* a, double* v, double2* cs, int2* pr,
     // sweep after ~1e-7; a stricter test never triggers for n >= 10)
     if (!(off > 1e-26 * (off + dia))) break;
     for (int r = 0; r < m - 1; ++r) {
-      // pair k of round r: (m-1, r) for k = 0, else (r+k, r-k) mod (m-1);
-      // a pair with the dummy player n (n odd) becomes (j, j)
       if (i < npairs) {
-        int p, q;
-        if (i == 0) {
-          p = r;
-          q = m - 1;
-        } else {
-          p = r + i;
-          if (p >= m - 1) p -= m - 1;
-          q = r - i;
-          if (q < 0) q += m - 1;
-        }
-        if (q >= n) q = p;
-        if (p >= n) p = q;
-        if (p > q) { const int t = p; p = q; q = t; }
-        double c = 1.0, s = 0.0;
-        const double apq = a[p * ld + q];
-        if (p != q && apq != 0.0) {
-          const double app = a[p * ld + p];
-          const double aqq = a[q * ld + q];
-          const double tau = (aqq - app) / (2.0 * apq);
-          double t;
-          if (fabs(tau) > 1e150) {
-            t = 0.5 / tau;
-          } else {
-            t = 1.0 / (fabs(tau) + sqrt(1.0 + tau * tau));
-            if (tau < 0.0) t = -t;
-          }
-          c = 1.0 / sqrt(1.0 + t * t);
-          s = t * c;
-        }
-        pr[i] = make_int2(p, q);
-        cs[p] = make_double2(c, -s);  // row/col p: x_p' = c x_p - s x_q
-        part[p] = q;
-        if (q != p) {
-          cs[q] = make_double2(c, s);  // row/col q: x_q' = c x_q + s x_p
-          part[q] = p;
-        }
+        jacobi_pair(a, ld, i, r, m, n, cs, pr, part);
       }
       lds_sync();
       const double2 ri = own ? cs[i] : make_double2(1.0, 0.0);
@@ -178,41 +245,18 @@ __device__ inline int wave_jacobi(double* a, double* v, double2* cs, int2* pr,
       constexpr int CH = 4;  // column pairs per chunk
       for (int k0 = 0; k0 < npairs; k0 += CH) {
         double na[CH], nb[CH], nv[CH], nw[CH];
-        int jj[CH], qq[CH];
+        int2 jq[CH];
 #pragma unroll
         for (int u = 0; u < CH; ++u) {
-          const int k = min(k0 + u, npairs - 1);
-          const int2 jq = pr[k];
-          const int j = jq.x, pj = jq.y;
-          jj[u] = j;
-          qq[u] = pj;
-          const double2 rj = cs[j];
-          const double2 rq = cs[pj];
-          const double aij = a[row * ld + j];
-          const double aiq = a[row * ld + pj];
-          const double apj = a[pir * ld + j];
-          const double apq = a[pir * ld + pj];
-          const double vij = v[row * ld + j];
-          const double viq = v[row * ld + pj];
-          // row rotation then column rotation, summed symmetrically
-          const double r_j = ri.x * aij + ri.y * apj;   // R_ij
-          const double r_q = ri.x * aiq + ri.y * apq;   // R_i,pj
-          na[u] = rj.x * r_j + rj.y * r_q;              // A''_ij
-          nb[u] = rq.x * r_q + rq.y * r_j;              // A''_i,pj
-          nv[u] = rj.x * vij + rj.y * viq;
-          nw[u] = rq.x * viq + rq.y * vij;
+          jq[u] = pr[min(k0 + u, npairs - 1)];
+          jacobi_update_read(a, v, ld, row, pir, ri, jq[u], cs, na[u], nb[u], nv[u],
+                             nw[u]);
         }
         lds_sync();
         if (own) {
 #pragma unroll
-          for (int u = 0; u < CH; ++u) {
-            a[i * ld + jj[u]] = na[u];
-            v[i * ld + jj[u]] = nv[u];
-            if (qq[u] != jj[u]) {
-              a[i * ld + qq[u]] = nb[u];
-              v[i * ld + qq[u]] = nw[u];
-            }
-          }
+          for (int u = 0; u < CH; ++u)
+            jacobi_update_write(a, v, ld, i, jq[u], na[u], nb[u], nv[u], nw[u]);
         }
         lds_sync();
       }
@@ -262,42 +306,7 @@ __device__ inline int wg_jacobi(double* a, double* v, double2* cs, int2* pr,
     if (!(off > 1e-26 * (off + dia))) break;
     for (int r = 0; r < m - 1; ++r) {
       if (w == 0 && i < npairs) {
-        int p, q;
-        if (i == 0) {
-          p = r;
-          q = m - 1;
-        } else {
-          p = r + i;
-          if (p >= m - 1) p -= m - 1;
-          q = r - i;
-          if (q < 0) q += m - 1;
-        }
-        if (q >= n) q = p;
-        if (p >= n) p = q;
-        if (p > q) { const int t = p; p = q; q = t; }
-        double c = 1.0, s = 0.0;
-        const double apq = a[p * ld + q];
-        if (p != q && apq != 0.0) {
-          const double app = a[p * ld + p];
-          const double aqq = a[q * ld + q];
-          const double tau = (aqq - app) / (2.0 * apq);
-          double t;
-          if (fabs(tau) > 1e150) {
-            t = 0.5 / tau;
-          } else {
-            t = 1.0 / (fabs(tau) + sqrt(1.0 + tau * tau));
-            if (tau < 0.0) t = -t;
-          }
-          c = 1.0 / sqrt(1.0 + t * t);
-          s = t * c;
-        }
-        pr[i] = make_int2(p, q);
-        cs[p] = make_double2(c, -s);
-        part[p] = q;
-        if (q != p) {
-          cs[q] = make_double2(c, s);
-          part[q] = p;
-        }
+        jacobi_pair(a, ld, i, r, m, n, cs, pr, part);
       }
       __syncthreads();
       const double2 ri = own ? cs[i] : make_double2(1.0, 0.0);
@@ -308,40 +317,18 @@ __device__ inline int wg_jacobi(double* a, double* v, double2* cs, int2* pr,
       constexpr int CH = 4;  // column pairs per chunk
       for (int k0 = kb; k0 < ke; k0 += CH) {
         double na[CH], nb[CH], nv[CH], nw[CH];
-        int jj[CH], qq[CH];
+        int2 jq[CH];
 #pragma unroll
         for (int u = 0; u < CH; ++u) {
-          const int k = min(k0 + u, ke - 1);
-          const int2 jq = pr[k];
-          const int j = jq.x, pj = jq.y;
-          jj[u] = j;
-          qq[u] = pj;
-          const double2 rj = cs[j];
-          const double2 rq = cs[pj];
-          const double aij = a[row * ld + j];
-          const double aiq = a[row * ld + pj];
-          const double apj = a[pir * ld + j];
-          const double apq = a[pir * ld + pj];
-          const double vij = v[row * ld + j];
-          const double viq = v[row * ld + pj];
-          const double r_j = ri.x * aij + ri.y * apj;
-          const double r_q = ri.x * aiq + ri.y * apq;
-          na[u] = rj.x * r_j + rj.y * r_q;
-          nb[u] = rq.x * r_q + rq.y * r_j;
-          nv[u] = rj.x * vij + rj.y * viq;
-          nw[u] = rq.x * viq + rq.y * vij;
+          jq[u] = pr[min(k0 + u, ke - 1)];
+          jacobi_update_read(a, v, ld, row, pir, ri, jq[u], cs, na[u], nb[u], nv[u],
+                             nw[u]);
         }
         lds_sync();
         if (own) {
 #pragma unroll
-          for (int u = 0; u < CH; ++u) {
-            a[i * ld + jj[u]] = na[u];
-            v[i * ld + jj[u]] = nv[u];
-            if (qq[u] != jj[u]) {
-              a[i * ld + qq[u]] = nb[u];
-              v[i * ld + qq[u]] = nw[u];
-            }
-          }
+          for (int u = 0; u < CH; ++u)
+            jacobi_update_write(a, v, ld, i, jq[u], na[u], nb[u], nv[u], nw[u]);
         }
         lds_sync();
       }
@@ -353,10 +340,11 @@ __device__ inline int wg_jacobi(double* a, double* v, double2* cs, int2* pr,
 
 // Rank of lane i's eigenvalue by descending |lambda| (ties by index), i.e.
 // the column order of U from svd() of a symmetric matrix.  Writes
-// perm[rank] = i for i < n.
-__device__ inline void wave_eig_order(const double* a, int n, int ld,
-                                      int* perm) {
-  const int i = lane();
+// perm[rank] = i for the team's lanes i < n.
+template <class Team>
+__device__ inline void eig_order(const Team& tm, const double* a, int n, int ld,
+                                 int* perm) {
+  const int i = tm.lane();
   if (i < n) {
     const double li = fabs(a[i * ld + i]);
     int rank = 0;
@@ -366,7 +354,7 @@ __device__ inline void wave_eig_order(const double* a, int n, int ld,
     }
     perm[rank] = i;
   }
-  lds_sync();
+  tm.sync();
 }
 
 // In-place Cholesky G = L L^T of the SPD k x k matrix g (lower triangle
