@@ -222,6 +222,21 @@ int sf_device_cus(sf_ctx* ctx, int* n_cu);
  * launch; 1 (default) = 3 for a fit pass with many new masks, else 2;
  * 0 = the Jacobi solve for every mask.  1, 2 and 3 write the same bits. */
 #define SF_OPT_FIT_SUBSET_DELETION 18
+/* SF_OPT_FIT_WIDE_CACHE: the mask cache of the fit above SF_MAX_DIR
+ * directions (sf_set_basis_wide) -- 1 (default): every distinct flag mask of
+ * a call's input is decomposed once, into a pool that the slots carrying the
+ * mask share; 0: every flagged slot decomposes its own subset covariance.
+ * Same bits either way; any other value is SF_EINVAL.  Ignored for
+ * D <= SF_MAX_DIR. */
+#define SF_OPT_FIT_WIDE_CACHE 19
+/* SF_OPT_FIT_WIDE_POOL_MB: cap of that pool's device memory in MiB, 1..65536
+ * (0 = default: 2048).  An entry takes (D (D | 1) + 2 D) doubles: 2 GiB hold
+ * 16,008 masks at D = 128, 40,427 at D = 80.  Masks beyond the cap get no
+ * entry: their slots decompose their own subset (same bits). */
+#define SF_OPT_FIT_WIDE_POOL_MB 20
+/* SF_OPT_FIT_WIDE_POOL_MAX: cap of the pool's number of entries (0 = default:
+ * none beyond the byte cap); a small value forces the fallback above. */
+#define SF_OPT_FIT_WIDE_POOL_MAX 21
 #define SF_EVAL_KERNEL_AUTO 0
 #define SF_EVAL_KERNEL_TILE 1
 #define SF_EVAL_KERNEL_LDS4 2
@@ -281,8 +296,19 @@ int sf_set_basis(sf_ctx* ctx, const double* pp_host, int D, double r0,
  *  - sf_kl_fit keeps its contract (screen types, niter, nsigma,
  *    adjust_order, ref_ant / ant_offset / ref_phase, the block and
  *    reference-station skips, NULL resid / w_out / order_out) on the wide
- *    fit: one workgroup per slot, a slot with flagged directions decomposes
- *    its own subset covariance (no mask cache).  The SF_OPT_FIT_* options are
+ *    fit: one workgroup per slot.  Every distinct flag mask of the call's
+ *    input is decomposed once, before the first pass, into a pool of subset
+ *    bases keyed by the 128-bit mask (SF_OPT_FIT_WIDE_CACHE, _POOL_MB,
+ *    _POOL_MAX); a slot whose mask has an entry reads it, and a slot whose
+ *    mask has none -- the cache off, the pool full, or a mask that outlier
+ *    flags created in a later pass and that no slot of the input carries --
+ *    decomposes its own subset covariance.  Same bits in every case.  Every
+ *    sf_kl_fit rebuilds the pool; it lives until the next sf_kl_fit,
+ *    sf_set_basis*, sf_set_piercepoints or sf_destroy, so an idle context
+ *    can hold up to the pool cap (2 GiB by default; the largest pool any
+ *    call on this geometry built) plus up to 68 bytes per slot of the
+ *    largest call for the keys and the table and 16 bytes per entry.  The
+ *    other SF_OPT_FIT_* options are
  *    ignored above SF_MAX_DIR directions.  The context keeps a workspace
  *    for the matrices that do not fit the LDS: (3 - m) D (D | 1) doubles
  *    per workgroup of the persistent grid, m = matrices that fit 160 KiB,
@@ -290,8 +316,14 @@ int sf_set_basis(sf_ctx* ctx, const double* pp_host, int D, double r0,
  *    13 MiB at D = 80, none for D <= 79),
  *    freed by sf_destroy and by the next sf_set_basis* / sf_set_piercepoints;
  *  - sf_get_fit_stats reports in n_masks the number of subset
- *    decompositions the last fit ran, and n_general = 0;
- *  - sf_get_fit_pool returns SF_EINVAL (its mask keys are 64-bit).
+ *    decompositions the last fit ran -- pool entries built plus the
+ *    decompositions slots ran for themselves -- and n_general = 0.  With the
+ *    cache on it is never above the count with the cache off.  When the pool
+ *    overflows, which masks get entries follows the order the masks were
+ *    numbered in, which is not deterministic: the count may then vary from
+ *    run to run (the fit's output does not);
+ *  - sf_get_fit_pool returns SF_EINVAL (its mask keys are 64-bit);
+ *    sf_get_fit_pool_wide returns the pool.
  */
 int sf_set_basis_wide(sf_ctx* ctx, const double* pp_host, int D, double r0,
                       double beta);
@@ -353,6 +385,20 @@ int sf_get_fit_stats(sf_ctx* ctx, int* n_masks, int* n_general);
  * exist.  Synchronises.  SF_EINVAL on a wide-basis context. */
 int sf_get_fit_pool(sf_ctx* ctx, uint64_t* masks_host, double* entries_host,
                     int max_masks, int* n_masks);
+/* sf_get_fit_pool on a wide-basis context (sf_set_basis_wide with more than
+ * SF_MAX_DIR directions), with 128-bit keys: the pool entries the last
+ * sf_kl_fit built (none with SF_OPT_FIT_WIDE_CACHE = 0).  masks_host[2 i]
+ * holds the bits of directions 0..63 of entry i and masks_host[2 i + 1] those
+ * of directions 64..127 (bit = direction unflagged, n bits set in all);
+ * entries_host[i * (D*D + D)] is a [D][D] block whose leading n x n part
+ * holds the subset's eigenvectors (row = unflagged direction in index order,
+ * columns sorted by |lambda| descending, ties by index) followed by D slots
+ * whose first n hold its eigenvalues; the rest of an entry is zero.  Entries
+ * are in the order the masks were numbered, which is not deterministic;
+ * *n_masks = how many exist.  Synchronises.  SF_EINVAL on a context that
+ * does not hold a wide basis. */
+int sf_get_fit_pool_wide(sf_ctx* ctx, uint64_t* masks_host, double* entries_host,
+                         int max_masks, int* n_masks);
 
 /*
  * Pixel grid of the a-term image: X[nx], Y[ny] screen coordinates of the

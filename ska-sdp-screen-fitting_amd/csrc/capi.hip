@@ -53,13 +53,32 @@ int dev_alloc(T** p, size_t count) {
   return SF_OK;
 }
 
+// the mask cache of the wide fit: slot keys, table, pool
+void free_wide_cache(sf_ctx* ctx) {
+  hipFree(ctx->d_wkeys);
+  hipFree(ctx->d_wslot);
+  hipFree(ctx->d_wtab);
+  hipFree(ctx->d_wtab_id);
+  hipFree(ctx->d_wpool_mask);
+  hipFree(ctx->d_wpool);
+  ctx->d_wkeys = nullptr;
+  ctx->d_wslot = nullptr;
+  ctx->d_wtab = nullptr;
+  ctx->d_wtab_id = nullptr;
+  ctx->d_wpool_mask = nullptr;
+  ctx->d_wpool = nullptr;
+  ctx->wslot_cap = ctx->wtab_cap = ctx->wpool_mask_cap = ctx->wpool_cap = 0;
+  ctx->wide_pool_n = 0;
+}
+
 // A new geometry: the workspace of the wide fit (kl_fit_wide.hip) was sized
-// for the previous D.
+// for the previous D, and its pool holds the previous geometry's bases.
 void drop_wide(sf_ctx* ctx) {
   ctx->wide = 0;
   hipFree(ctx->d_wide_ws);
   ctx->d_wide_ws = nullptr;
   ctx->wide_ws_cap = 0;
+  free_wide_cache(ctx);
 }
 
 // No geometry, no grid, no points, wide state dropped: the context while a
@@ -112,6 +131,7 @@ int sf_destroy(sf_ctx* ctx) {
   hipFree(ctx->d_u);
   hipFree(ctx->d_eig);
   hipFree(ctx->d_wide_ws);
+  free_wide_cache(ctx);
   hipFree(ctx->d_cfrag);
   hipFree(ctx->d_pxy);
   hipFree(ctx->d_pfrag);
@@ -270,6 +290,21 @@ int sf_set_option(sf_ctx* ctx, int option, int value) {
       SF_REQUIRE(value >= 0 && value <= 4, SF_EINVAL,
                  "sf_set_option: fit eig waves must be 0..4");
       ctx->fit_eig_waves = value;
+      return SF_OK;
+    case SF_OPT_FIT_WIDE_CACHE:
+      SF_REQUIRE(value == 0 || value == 1, SF_EINVAL,
+                 "sf_set_option: fit wide cache must be 0 or 1");
+      ctx->wide_cache = value;
+      return SF_OK;
+    case SF_OPT_FIT_WIDE_POOL_MB:
+      SF_REQUIRE(value >= 0 && value <= 65536, SF_EINVAL,
+                 "sf_set_option: fit wide pool MiB must be 0..65536");
+      ctx->wide_pool_mb = value;
+      return SF_OK;
+    case SF_OPT_FIT_WIDE_POOL_MAX:
+      SF_REQUIRE(value >= 0, SF_EINVAL,
+                 "sf_set_option: negative fit wide pool entry cap");
+      ctx->wide_pool_max = value;
       return SF_OK;
     default:
       set_error("sf_set_option: unknown option");
@@ -503,8 +538,8 @@ int sf_get_fit_pool(sf_ctx* ctx, uint64_t* masks_host, double* entries_host,
   SF_REQUIRE(max_masks == 0 || (masks_host && entries_host), SF_EINVAL,
              "sf_get_fit_pool: NULL output");
   SF_REQUIRE(!ctx->wide, SF_EINVAL,
-             "sf_get_fit_pool: no mask pool above SF_MAX_DIR directions "
-             "(sf_set_basis_wide: every flagged slot decomposes its own subset)");
+             "sf_get_fit_pool: 64-bit mask keys; above SF_MAX_DIR directions "
+             "(sf_set_basis_wide) call sf_get_fit_pool_wide");
   SF_HIP(hipSetDevice(ctx->device));
   SF_HIP(hipStreamSynchronize(ctx->stream));
   int c0 = 0;
@@ -520,6 +555,24 @@ int sf_get_fit_pool(sf_ctx* ctx, uint64_t* masks_host, double* entries_host,
     SF_HIP(hipMemcpy(entries_host, ctx->d_pool, k * entry * sizeof(double),
                      hipMemcpyDeviceToHost));
   }
+  return SF_OK;
+}
+
+int sf_get_fit_pool_wide(sf_ctx* ctx, uint64_t* masks_host, double* entries_host,
+                         int max_masks, int* n_masks) {
+  SF_REQUIRE(ctx && n_masks && max_masks >= 0, SF_EINVAL,
+             "sf_get_fit_pool_wide: bad argument");
+  SF_REQUIRE(max_masks == 0 || (masks_host && entries_host), SF_EINVAL,
+             "sf_get_fit_pool_wide: NULL output");
+  SF_REQUIRE(ctx->wide && ctx->has_basis, SF_EINVAL,
+             "sf_get_fit_pool_wide: the context holds no wide basis "
+             "(sf_set_basis_wide with more than SF_MAX_DIR directions)");
+  SF_HIP(hipSetDevice(ctx->device));
+  SF_HIP(hipStreamSynchronize(ctx->stream));
+  const int n = ctx->wide_pool_n;
+  *n_masks = n;
+  const int k = n < max_masks ? n : max_masks;
+  if (k > 0) return sf::read_fit_pool_wide(ctx, masks_host, entries_host, k);
   return SF_OK;
 }
 

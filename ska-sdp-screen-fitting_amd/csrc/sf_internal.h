@@ -91,6 +91,22 @@ struct sf_ctx {
   // fit workgroups that do not fit the LDS
   double* d_wide_ws = nullptr;
   size_t wide_ws_cap = 0;      // doubles
+  // mask cache of the wide fit: every distinct flag mask of a call's input is
+  // decomposed once (128-bit keys; rebuilt by every sf_kl_fit)
+  int wide_cache = 1;          // SF_OPT_FIT_WIDE_CACHE
+  int wide_pool_mb = 0;        // SF_OPT_FIT_WIDE_POOL_MB (0 = 2048)
+  int wide_pool_max = 0;       // SF_OPT_FIT_WIDE_POOL_MAX (0 = no entry cap)
+  unsigned long long* d_wkeys = nullptr;  // [S][2] initial mask of every slot
+  int* d_wslot = nullptr;      // [S] table slot, then pool id, of that mask
+  size_t wslot_cap = 0;        // slots
+  unsigned long long* d_wtab = nullptr;   // [wtab_cap] claimant slot + 1 (0 = empty)
+  int* d_wtab_id = nullptr;    // [wtab_cap] pool id of a claimed table entry
+  size_t wtab_cap = 0;         // power of two
+  unsigned long long* d_wpool_mask = nullptr;  // [entries][2]
+  size_t wpool_mask_cap = 0;   // words (two per entry)
+  double* d_wpool = nullptr;   // [wide_pool_n][D (D | 1) + 2 D]: V, lam, perm
+  size_t wpool_cap = 0;        // doubles
+  int wide_pool_n = 0;         // entries the last fit built (for this D)
   // pixel grid (sf_set_grid)
   int nx = 0, ny = 0;
   int64_t n_pix = 0;
@@ -224,6 +240,8 @@ int launch_basis_wide(sf_ctx* ctx);
 int launch_fit_wide(sf_ctx* ctx, const double* phase, const float* weight,
                     int T, int F, int A, const sf_fit_params* p, double* coef,
                     double* resid, float* w_out, int32_t* order_out);
+// the wide fit's pool of subset bases in sf_get_fit_pool's layout (host)
+int read_fit_pool_wide(sf_ctx* ctx, uint64_t* masks, double* entries, int k);
 int launch_cpix(sf_ctx* ctx, const double* d_x, const double* d_y);
 int launch_cdig(sf_ctx* ctx, const double* d_x, const double* d_y, int* d_bad);
 int launch_fit(sf_ctx* ctx, const double* phase, const float* weight, int T,

@@ -43,6 +43,9 @@ SF_OPT_EVAL_INT = 15
 SF_OPT_EVAL_WG_WAVES = 16
 SF_OPT_FIT_EIG_WAVES = 17
 SF_OPT_FIT_SUBSET_DELETION = 18
+SF_OPT_FIT_WIDE_CACHE = 19
+SF_OPT_FIT_WIDE_POOL_MB = 20
+SF_OPT_FIT_WIDE_POOL_MAX = 21
 SF_EVAL_KERNEL_AUTO = 0
 SF_EVAL_KERNEL_TILE = 1
 SF_EVAL_KERNEL_LDS4 = 2
@@ -68,6 +71,7 @@ EXPORTED = (
     "sf_version", "sf_last_error", "sf_create", "sf_destroy", "sf_set_stream",
     "sf_synchronize", "sf_set_option", "sf_get_eval_kernel", "sf_get_eval_contraction", "sf_alloc", "sf_free", "sf_copy_h2d", "sf_copy_d2h",
     "sf_set_basis", "sf_set_basis_wide", "sf_set_piercepoints", "sf_get_basis", "sf_kl_fit", "sf_get_fit_stats", "sf_get_fit_pool",
+    "sf_get_fit_pool_wide",
     "sf_stream_create", "sf_stream_destroy", "sf_device_cus",
     "sf_set_grid", "sf_kl_eval", "sf_kl_eval_gain", "sf_kl_eval_sums",
     "sf_tess_fill", "sf_smooth",
@@ -147,6 +151,7 @@ def load_library(path=None):
                            ctypes.POINTER(FitParams), vp, vp, vp, vp], c_int),
             "sf_get_fit_stats": ([vp, ip, ip], c_int),
             "sf_get_fit_pool": ([vp, vp, vp, c_int, ip], c_int),
+            "sf_get_fit_pool_wide": ([vp, vp, vp, c_int, ip], c_int),
             "sf_set_grid": ([vp, vp, c_int, vp, c_int], c_int),
             "sf_kl_eval": ([vp, vp, i64, vp, i64, ctypes.c_uint], c_int),
             "sf_stream_create": ([vp, ctypes.POINTER(c_int), c_int,
@@ -281,7 +286,8 @@ class Context:
     def set_basis_wide(self, pp, r0=100.0, beta=5.0 / 3.0):
         """sf_set_basis_wide: the basis for up to SF_MAX_FIT_DIR directions
         (``set_basis`` itself up to SF_MAX_DIR; above, the workgroup-per-slot
-        fit and the wide evaluation serve; ``fit_pool`` raises there)."""
+        fit and the wide evaluation serve; ``fit_pool`` raises there,
+        ``fit_pool_wide`` returns the fit's pool of subset bases)."""
         pp = np.ascontiguousarray(pp, dtype=np.float64)
         assert pp.ndim == 2 and pp.shape[1] == 3
         self.D = 0
@@ -367,6 +373,24 @@ class Context:
             u[:, n:] = 0.0
             ent[k, D * D + n:] = 0.0
         return masks, ent
+
+    def fit_pool_wide(self):
+        """The subset bases the last wide fit built (sf_get_fit_pool_wide),
+        sorted by (hi, lo): (masks uint64 [n][2] -- lo = directions 0..63,
+        hi = 64..127 -- entries float64 [n][D*D + D])."""
+        n = ctypes.c_int(0)
+        _check(self.lib.sf_get_fit_pool_wide(self.h, None, None, 0, ctypes.byref(n)),
+               "sf_get_fit_pool_wide")
+        D = self.D
+        masks = np.zeros((n.value, 2), np.uint64)
+        ent = np.zeros((n.value, D * D + D))
+        if n.value:
+            _check(self.lib.sf_get_fit_pool_wide(self.h, masks.ctypes.data,
+                                                 ent.ctypes.data, n.value,
+                                                 ctypes.byref(n)),
+                   "sf_get_fit_pool_wide")
+        order = np.lexsort((masks[:, 0], masks[:, 1]))
+        return masks[order], ent[order]
 
     def set_grid(self, x, y):
         x = np.ascontiguousarray(x, dtype=np.float64)
