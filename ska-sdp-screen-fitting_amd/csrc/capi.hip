@@ -522,13 +522,15 @@ int sf_kl_fit(sf_ctx* ctx, const double* phase, const float* weight, int T,
 
 int sf_get_fit_stats(sf_ctx* ctx, int* n_masks, int* n_general) {
   SF_REQUIRE(ctx, SF_EINVAL, "sf_get_fit_stats: NULL context");
-  int c[4] = {0, 0, 0, 0};
+  int c[sf::kFitCounters] = {};
   SF_HIP(hipSetDevice(ctx->device));
   SF_HIP(hipStreamSynchronize(ctx->stream));
   if (ctx->d_counters)
     SF_HIP(hipMemcpy(c, ctx->d_counters, sizeof(c), hipMemcpyDeviceToHost));
-  if (n_masks) *n_masks = c[0];
-  if (n_general) *n_general = c[2];
+  // the wide fit counts its subset decompositions in the same slot
+  static_assert(sf::kCntIds == sf::kCntWideDecomp, "n_masks reads one slot");
+  if (n_masks) *n_masks = c[sf::kCntIds];
+  if (n_general) *n_general = c[sf::kCntSlow];
   return SF_OK;
 }
 
@@ -544,7 +546,8 @@ int sf_get_fit_pool(sf_ctx* ctx, uint64_t* masks_host, double* entries_host,
   SF_HIP(hipStreamSynchronize(ctx->stream));
   int c0 = 0;
   if (ctx->d_counters)
-    SF_HIP(hipMemcpy(&c0, ctx->d_counters, sizeof(int), hipMemcpyDeviceToHost));
+    SF_HIP(hipMemcpy(&c0, ctx->d_counters + sf::kCntIds, sizeof(int),
+                     hipMemcpyDeviceToHost));
   const int n = ctx->pool_D == ctx->D && (size_t)c0 <= ctx->pool_cap ? c0 : 0;
   *n_masks = n;
   const int k = n < max_masks ? n : max_masks;

@@ -145,7 +145,6 @@ __host__ __device__ inline size_t fit_wave_bytes(int D) {
 }
 
 __global__ __launch_bounds__(256) void kl_fit_general_kernel(
-    const int* __restrict__ slot_list, const int* __restrict__ n_list,
     const double* __restrict__ phase, const float* __restrict__ weight,
     int T, int F, int A, int D, const int* __restrict__ st_order,
     const uint8_t* __restrict__ skip, const double* __restrict__ refph,
@@ -186,14 +185,11 @@ __global__ __launch_bounds__(256) void kl_fit_general_kernel(
   for (int e = threadIdx.x; e < D; e += blockDim.x) L.eig[e] = g_eig[e];
   __syncthreads();
 
-  // either all slots or the slots of a device-side list (the slow path of
-  // kl_fit_fast.hip: tiny weights, mask-pool overflow)
-  const int64_t S = slot_list ? (int64_t)n_list[0] : (int64_t)T * F * A;
-  for (int64_t j = (int64_t)blockIdx.x * nwaves + wv; j < S;
-       j += (int64_t)gridDim.x * nwaves) {
-    const int64_t s = slot_list ? (int64_t)slot_list[j] : j;
-    const int a = (int)(s % A);
-    const int f = (int)((s / A) % F);
+  const int64_t S = (int64_t)T * F * A;
+  for (int64_t s = (int64_t)blockIdx.x * nwaves + wv; s < S;
+       s += (int64_t)gridDim.x * nwaves) {
+    const SlotGeom g(s, F, A);
+    const int a = g.a;
     const int64_t base = s * D;
     double phi_d = 0.0;
     float w_f = 0.0f;
@@ -201,8 +197,7 @@ __global__ __launch_bounds__(256) void kl_fit_general_kernel(
       phi_d = phase_ref(phase, refph, ref, s, a, A, D, d);
       w_f = weight[base + d];
     }
-    const bool skipped = (ref_skip >= 0 && a == ref_skip) || skip[f * A + a];
-    if (skipped) {
+    if (g.skipped(skip, ref_skip)) {
       if (d < D) {
         coef[base + d] = 0.0;
         if (resid_out) resid_out[base + d] = 0.0;
@@ -307,28 +302,23 @@ int launch_skip(sf_ctx* ctx, const double* phase, const float* weight, int T,
   return SF_OK;
 }
 
-int launch_fit_general(sf_ctx* ctx, const int* slot_list, const int* n_list,
-                       int64_t max_slots, const double* phase,
-                       const float* weight, int T, int F, int A,
-                       const sf_fit_params* p, const RefSpec& r, double* coef,
-                       double* resid, float* w_out, int32_t* order_out) {
+int launch_fit_general(sf_ctx* ctx, const double* phase, const float* weight,
+                       int T, int F, int A, const sf_fit_params* p,
+                       const RefSpec& r, double* coef, double* resid,
+                       float* w_out, int32_t* order_out) {
   const int D = ctx->D;
   const size_t shared = fit_shared_bytes(D);
   const size_t wave = fit_wave_bytes(D);
   int nw = 4;
   while (nw > 1 && shared + nw * wave > 80 * 1024) --nw;
   const size_t shm = shared + nw * wave;
-  int64_t blocks = (max_slots + nw - 1) / nw;
+  int64_t blocks = ((int64_t)T * F * A + nw - 1) / nw;
   if (blocks > 4096) blocks = 4096;
   if (blocks < 1) blocks = 1;
-  if (shm > 64 * 1024)
-    SF_HIP(hipFuncSetAttribute(
-        reinterpret_cast<const void*>(&kl_fit_general_kernel),
-        hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm));
+  SF_TRY_RC(allow_lds(kl_fit_general_kernel, shm));
   hipLaunchKernelGGL(kl_fit_general_kernel, dim3((unsigned)blocks),
-                     dim3(64 * nw), shm, ctx->stream, slot_list, n_list, phase,
-                     weight, T, F, A, D, ctx->d_st_order, ctx->d_skip, r.refph,
-                     ctx->d_c, ctx->d_u, ctx->d_eig, p->screen_type, p->niter,
+                     dim3(64 * nw), shm, ctx->stream, phase, weight, T, F, A, D,
+                     ctx->d_st_order, ctx->d_skip, r.refph, ctx->d_c, ctx->d_u, ctx->d_eig, p->screen_type, p->niter,
                      p->nsigma, p->adjust_order, r.sub, r.skip, coef, resid,
                      w_out, order_out);
   SF_HIP(hipGetLastError());

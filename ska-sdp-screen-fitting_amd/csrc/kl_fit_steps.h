@@ -80,6 +80,18 @@ __device__ __forceinline__ double phase_ref(const double* phase,
   return v;
 }
 
+// Where slot s = (t * F + f) * A + a sits: its station, frequency and
+// (station, freq) block, and whether no pass fits it -- the reference
+// station's slots and the skipped blocks (stationscreen.py:818-825)
+struct SlotGeom {
+  int a, f, blk;
+  __device__ __forceinline__ SlotGeom(int64_t s, int F, int A)
+      : a((int)(s % A)), f((int)((s / A) % F)), blk(f * A + a) {}
+  __device__ __forceinline__ bool skipped(const uint8_t* skip, int ref_skip) const {
+    return a == ref_skip || skip[blk];
+  }
+};
+
 // amplitude screens are log10 values (stationscreen.py:535-548, 576-588)
 template <class Math = FitMath<false>>
 __device__ __forceinline__ double model_value(int screen_type, double x) {

@@ -38,6 +38,7 @@
 
 #include "kl_cov.h"
 #include "kl_fit_exact.h"
+#include "kl_fit_masks.h"
 #include "kl_fit_wide.h"
 #include "sf_internal.h"
 
@@ -107,7 +108,7 @@ struct WideFit {
   double* lam;         // S->lam, idx, perm: the subset state
   int* idx;
   int* perm;
-  int* counters;       // [0]: subset decompositions run
+  int* counters;       // d_counters: kCntWideDecomp counts the decompositions
   int D, ld;
   // C is symmetric: thread r reads along the row of q (coalesced)
   __device__ double csym(int r, int q) const { return gC[(size_t)q * D + r]; }
@@ -121,7 +122,7 @@ struct WideFit {
     wide_cholesky_solve2(g, k, ld_, b1, b2, S->red);
   }
   __device__ void decomposed() const {
-    if (threadIdx.x == 0) atomicAdd(counters, 1);
+    if (threadIdx.x == 0) atomicAdd(counters + kCntWideDecomp, 1);
   }
 };
 
@@ -160,15 +161,14 @@ __global__ __launch_bounds__(256) void kl_wide_init_kernel(
   if (e >= S * D) return;
   const int64_t s = e / D;
   const int d = (int)(e % D);
-  const int a = (int)(s % A);
-  const int f = (int)((s / A) % F);
-  const bool skipped = a == ref_skip || skip[f * A + a];
+  const SlotGeom g(s, F, A);
+  const bool skipped = g.skipped(skip, ref_skip);
   w_out[e] = weight[e];
   if (skipped) {
     coef[e] = 0.0;
     resid[e] = 0.0;
   }
-  if (d == 0) order_out[s] = skipped ? 0 : st_order[a];
+  if (d == 0) order_out[s] = skipped ? 0 : st_order[g.a];
 }
 
 // tec / amplitude: |diff| > nsigma sigma(block) -> weight 0
@@ -182,11 +182,10 @@ __global__ __launch_bounds__(256) void kl_wide_block_flag_kernel(
   if (e >= S * D) return;
   const int64_t s = e / D;
   const int d = (int)(e % D);
-  const int a = (int)(s % A);
-  const int f = (int)((s / A) % F);
-  if (a == ref_skip || skip[f * A + a]) return;
-  const double sig = sigma[f * A + a];
-  const double v = phase_ref(phase, refph, ref_sub, s, a, A, D, d);
+  const SlotGeom g(s, F, A);
+  if (g.skipped(skip, ref_skip)) return;
+  const double sig = sigma[g.blk];
+  const double v = phase_ref(phase, refph, ref_sub, s, g.a, A, D, d);
   const double sd = screen_diff(screen_type, v, resid[e]);
   if (fabs(sd) > nsigma * sig && w_out[e] != 0.0f) w_out[e] = 0.0f;
 }
@@ -212,17 +211,9 @@ struct WidePool {
   int n;
 };
 
-__device__ __forceinline__ unsigned long long wide_mix(unsigned long long x) {
-  x ^= x >> 30;
-  x *= 0xbf58476d1ce4e5b9ull;
-  x ^= x >> 27;
-  x *= 0x94d049bb133111ebull;
-  x ^= x >> 31;
-  return x;
-}
 __device__ __forceinline__ int wide_hash(unsigned long long lo,
                                          unsigned long long hi, int cap) {
-  return (int)(wide_mix(wide_mix(lo ^ 0x9e3779b97f4a7c15ull) + hi) &
+  return (int)(mix64(mix64(lo ^ 0x9e3779b97f4a7c15ull) + hi) &
                (unsigned long long)(cap - 1));
 }
 
@@ -239,9 +230,7 @@ __global__ __launch_bounds__(256) void kl_wide_keys_kernel(
   const float* w = weight + s * D;
   const unsigned long long lo = __ballot(l < D && w[l] > 0.0f);
   const unsigned long long hi = __ballot(l + 64 < D && w[l + 64] > 0.0f);
-  const int a = (int)(s % A);
-  const int f = (int)((s / A) % F);
-  const bool skipped = a == ref_skip || skip[f * A + a];
+  const bool skipped = SlotGeom(s, F, A).skipped(skip, ref_skip);
   if (l == 0) {
     keys[2 * s] = skipped ? 0ull : lo;
     keys[2 * s + 1] = skipped ? 0ull : hi;
@@ -282,33 +271,22 @@ __global__ __launch_bounds__(256) void kl_wide_insert_kernel(
   slot_pos[s] = pos;
 }
 
-// number the claimed entries (one atomic per wavefront, as kl_assign_kernel)
-// and copy their keys to pool_mask (ids below mask_cap)
+// number the claimed entries (number_fresh, as kl_assign_kernel) and copy
+// their claimants' keys to pool_mask (ids below mask_cap)
 __global__ __launch_bounds__(256) void kl_wide_assign_kernel(
     const unsigned long long* __restrict__ tab, int cap,
     const unsigned long long* __restrict__ keys, int* __restrict__ tab_id,
     unsigned long long* __restrict__ pool_mask, int mask_cap,
     int* __restrict__ count) {
-  // grid-stride over the table (a power of two >= 64: every wave's lanes
-  // take the same trips)
-  for (int i = blockIdx.x * blockDim.x + threadIdx.x; i - lane() < cap;
+  for (int i = blockIdx.x * blockDim.x + threadIdx.x; wave_in_table(i, cap);
        i += gridDim.x * blockDim.x) {
     const unsigned long long e = i < cap ? tab[i] : 0ull;
-    const bool fresh = e != 0ull;
-    const unsigned long long nb = __ballot(fresh);
-    if (nb == 0ull) continue;  // wave-uniform
-    int base = 0;
-    if (lane() == 0) base = atomicAdd(count, __popcll(nb));
-    base = __shfl(base, 0);
-    if (fresh) {
-      const int id = base + __builtin_amdgcn_mbcnt_hi(
-                                (uint32_t)(nb >> 32),
-                                __builtin_amdgcn_mbcnt_lo((uint32_t)nb, 0));
-      tab_id[i] = id;
-      if (id < mask_cap) {
-        pool_mask[2 * (size_t)id] = keys[2 * (e - 1ull)];
-        pool_mask[2 * (size_t)id + 1] = keys[2 * (e - 1ull) + 1];
-      }
+    const int id = number_fresh(e != 0ull, count);
+    if (id < 0) continue;
+    tab_id[i] = id;
+    if (id < mask_cap) {
+      pool_mask[2 * (size_t)id] = keys[2 * (e - 1ull)];
+      pool_mask[2 * (size_t)id + 1] = keys[2 * (e - 1ull) + 1];
     }
   }
 }
@@ -469,9 +447,9 @@ __global__ __launch_bounds__(kWideThreads) void kl_fit_wide_kernel(
   const size_t entry = wide_entry_doubles(D);
 
   for (int64_t s = blockIdx.x; s < nslots; s += gridDim.x) {
-    const int a = (int)(s % A);
-    const int f = (int)((s / A) % F);
-    if (a == ref_skip || skip[f * A + a]) continue;  // workgroup-uniform
+    const SlotGeom g(s, F, A);
+    const int a = g.a;
+    if (g.skipped(skip, ref_skip)) continue;  // workgroup-uniform
     const int64_t base = s * D;
     double phi_d = 0.0, w_d = 0.0, white_d = 0.0, resid_d = 0.0;
     if (live) {
@@ -560,12 +538,6 @@ int wide_lds_mats(int D) {
   return n > 3 ? 3 : (int)n;
 }
 
-size_t next_pow2(size_t x) {
-  size_t p = 64;
-  while (p < x) p <<= 1;
-  return p;
-}
-
 // The mask cache of one fit, built before pass 0: the slots' masks, the
 // table, the numbering (read back, as the <= 60 path reads its new-mask
 // count), the pool sized min(distinct masks, SF_OPT_FIT_WIDE_POOL_MAX,
@@ -581,30 +553,14 @@ int build_wide_pool(sf_ctx* ctx, const float* weight, int64_t S, int F, int A,
     max_entries = (size_t)ctx->wide_pool_max;
   if (max_entries > (size_t)S) max_entries = (size_t)S;
   if (max_entries == 0) return SF_OK;
-  if (ctx->wslot_cap < (size_t)S) {
-    size_t c1 = 0, c2 = 0;
-    if (ctx->d_wkeys) (void)hipFree(ctx->d_wkeys);
-    if (ctx->d_wslot) (void)hipFree(ctx->d_wslot);
-    ctx->d_wkeys = nullptr;
-    ctx->d_wslot = nullptr;
-    ctx->wslot_cap = 0;
-    SF_TRY_RC(grow(&ctx->d_wkeys, c1, (size_t)2 * S));
-    SF_TRY_RC(grow(&ctx->d_wslot, c2, (size_t)S));
-    ctx->wslot_cap = (size_t)S;
-  }
+  if (ctx->wslot_cap < (size_t)S)
+    SF_TRY_RC(replace_pair(ctx->wslot_cap, (size_t)S, &ctx->d_wkeys, (size_t)2 * S,
+                           &ctx->d_wslot, (size_t)S));
   // at most one insert per slot: the table stays half empty
-  const size_t tcap = next_pow2((size_t)2 * S);
-  if (ctx->wtab_cap < tcap) {
-    size_t c1 = 0, c2 = 0;
-    if (ctx->d_wtab) (void)hipFree(ctx->d_wtab);
-    if (ctx->d_wtab_id) (void)hipFree(ctx->d_wtab_id);
-    ctx->d_wtab = nullptr;
-    ctx->d_wtab_id = nullptr;
-    ctx->wtab_cap = 0;
-    SF_TRY_RC(grow(&ctx->d_wtab, c1, tcap));
-    SF_TRY_RC(grow(&ctx->d_wtab_id, c2, tcap));
-    ctx->wtab_cap = tcap;
-  }
+  const size_t tcap = next_pow2((size_t)2 * S, 64);
+  if (ctx->wtab_cap < tcap)
+    SF_TRY_RC(replace_pair(ctx->wtab_cap, tcap, &ctx->d_wtab, tcap, &ctx->d_wtab_id,
+                           tcap));
   SF_TRY_RC(grow(&ctx->d_wpool_mask, ctx->wpool_mask_cap, 2 * max_entries));
   const int cap = (int)ctx->wtab_cap;
   SF_HIP(hipMemsetAsync(ctx->d_wtab, 0, ctx->wtab_cap * sizeof(unsigned long long),
@@ -617,7 +573,7 @@ int build_wide_pool(sf_ctx* ctx, const float* weight, int64_t S, int F, int A,
                      dim3(256), 0, ctx->stream, ctx->d_wkeys, S, D, ctx->d_wtab,
                      cap, ctx->d_wslot);
   SF_HIP(hipGetLastError());
-  int* count = ctx->d_counters + 6;
+  int* count = ctx->d_counters + kCntWideMasks;
   hipLaunchKernelGGL(kl_wide_assign_kernel,
                      dim3((unsigned)((cap + 255) / 256 < 8192 ? (cap + 255) / 256 : 8192)),
                      dim3(256), 0, ctx->stream, ctx->d_wtab, cap, ctx->d_wkeys,
@@ -637,10 +593,7 @@ int build_wide_pool(sf_ctx* ctx, const float* weight, int64_t S, int F, int A,
   const int v_lds = wide_lds_mats(D) >= 2;
   const size_t shm = sizeof(WideSmall) +
                      (size_t)(v_lds ? 2 : 1) * D * odd_ld(D) * sizeof(double);
-  if (shm > 64 * 1024)
-    SF_HIP(hipFuncSetAttribute(
-        reinterpret_cast<const void*>(&kl_wide_subset_kernel),
-        hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm));
+  SF_TRY_RC(allow_lds(kl_wide_subset_kernel, shm));
   const int grid = n_cu > 0 && n_cu < n ? n_cu : n;
   hipLaunchKernelGGL(kl_wide_subset_kernel, dim3((unsigned)grid),
                      dim3(kWideThreads), shm, ctx->stream, n, D, v_lds, ctx->d_c,
@@ -711,7 +664,7 @@ int launch_fit_wide(sf_ctx* ctx, const double* phase, const float* weight,
                      ctx->d_skip);
   SF_HIP(hipGetLastError());
   SF_TRY_RC(fit_buffers(ctx, S, F, A, &resid, &w_out, &order_out));
-  SF_HIP(hipMemsetAsync(ctx->d_counters, 0, 8 * sizeof(int), ctx->stream));
+  SF_HIP(hipMemsetAsync(ctx->d_counters, 0, kFitCounters * sizeof(int), ctx->stream));
 
   // persistent grid: one workgroup per CU (the kernel's registers and, from
   // D = 61, its LDS leave room for no second one), never more than slots;
@@ -726,10 +679,7 @@ int launch_fit_wide(sf_ctx* ctx, const double* phase, const float* weight,
   if (grid > S) grid = S;
   const size_t ws = (size_t)grid * (size_t)(3 - nl) * mat;
   if (ws > 0) SF_TRY_RC(grow(&ctx->d_wide_ws, ctx->wide_ws_cap, ws));
-  if (shm > 64 * 1024)
-    SF_HIP(hipFuncSetAttribute(
-        reinterpret_cast<const void*>(&kl_fit_wide_kernel),
-        hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm));
+  SF_TRY_RC(allow_lds(kl_fit_wide_kernel, shm));
 
   WidePool pool = {};
   ctx->wide_pool_n = 0;

@@ -59,6 +59,53 @@ int grow(T** p, size_t& cap, size_t need, bool keep = false) {
   return SF_OK;
 }
 
+// Two buffers sized together, replaced, not kept: both are freed before
+// either is allocated, so the old and the new pair never coexist.  `cap` is
+// the pair's size in the caller's unit (0 while either buffer is missing).
+template <typename T, typename U>
+int replace_pair(size_t& cap, size_t new_cap, T** p, size_t np, U** q, size_t nq) {
+  if (*p) (void)hipFree(*p);
+  if (*q) (void)hipFree(*q);
+  *p = nullptr;
+  *q = nullptr;
+  cap = 0;
+  size_t cp = 0, cq = 0;
+  SF_TRY_RC(grow(p, cp, np));
+  SF_TRY_RC(grow(q, cq, nq));
+  cap = new_cap;
+  return SF_OK;
+}
+
+// A kernel launched with more than 64 KiB of dynamic LDS has to be allowed it
+template <typename K>
+int allow_lds(K* kernel, size_t shm) {
+  if (shm > 64 * 1024)
+    SF_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kernel),
+                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm));
+  return SF_OK;
+}
+
+// ctx->d_counters: kFitCounters ints, zeroed at the start of every fit
+enum FitCounter {
+  kCntIds = 0,         // <= 60 directions: pool ids issued so far
+  kCntWideDecomp = 0,  // wide fit: subset decompositions run.  An alias of
+                       // kCntIds (the wide fit issues no ids there), so
+                       // sf_get_fit_stats reports either as n_masks
+  kCntPassStart = 1,   // start of this pass's id range [start, ids)
+  kCntSlow = 2,        // slow-class slots (a weight in (0, 1.001e-3])
+  kCntError = 3,       // FitError bits
+  kCntNonUniform = 4,  // fast-class slots with unequal positive weights
+  kCntMaxLevel = 5,    // deepest deletion level among this pass's new masks
+  kCntWideMasks = 6,   // wide fit: distinct masks numbered
+};
+constexpr int kFitCounters = 8;
+enum FitError {
+  kErrLookupMiss = 1,      // a slot's mask has no pool id
+  kErrTableFull = 2,       // the mask table took no further key
+  kErrLeanNonUniform = 4,  // the lean pass met non-uniform weights
+  kErrFullMaskInPool = 8,  // a mask with no flagged direction in the pool
+};
+
 // pixel tiling of the evaluation kernel (kl_eval.hip) -------------------------
 constexpr int kTiles = 4;                       // 16x16 MFMA tiles per wave, interleaved
 constexpr int kWavePix = 16 * kTiles;           // 64 consecutive pixels per wave
@@ -160,8 +207,7 @@ struct sf_ctx {
   double* d_sigma = nullptr;             // [F][A] tec/amplitude block sigma
   size_t sigma_cap = 0;
   size_t slot_cap = 0;
-  int* d_counters = nullptr;  // [0] ids, [1] range start, [2] slow, [3] error,
-                              // [4] non-uniform-weight slots
+  int* d_counters = nullptr;  // [kFitCounters], indexed by sf::FitCounter
   size_t counters_cap = 0;
   double* d_scratch = nullptr;           // resid / state when caller passes NULL
   size_t scratch_cap = 0;
@@ -220,11 +266,10 @@ struct RefSpec {
 RefSpec ref_spec(const sf_fit_params* p, int A);
 int launch_skip(sf_ctx* ctx, const double* phase, const float* weight, int T,
                 int F, int A, const RefSpec& r);
-int launch_fit_general(sf_ctx* ctx, const int* slot_list, const int* n_list,
-                       int64_t max_slots, const double* phase,
-                       const float* weight, int T, int F, int A,
-                       const sf_fit_params* p, const RefSpec& r, double* coef,
-                       double* resid, float* w_out, int32_t* order_out);
+int launch_fit_general(sf_ctx* ctx, const double* phase, const float* weight,
+                       int T, int F, int A, const sf_fit_params* p,
+                       const RefSpec& r, double* coef, double* resid,
+                       float* w_out, int32_t* order_out);
 int launch_basis(sf_ctx* ctx);
 // tec / amplitude outlier sigma per (station, freq) block into ctx->d_sigma
 // (kl_block_sigma_kernel, kl_fit_fast.hip; any D)

@@ -338,22 +338,39 @@ __device__ inline int wg_jacobi(double* a, double* v, double2* cs, int2* pr,
   return sweep;
 }
 
-// Rank of lane i's eigenvalue by descending |lambda| (ties by index), i.e.
-// the column order of U from svd() of a symmetric matrix.  Writes
-// perm[rank] = i for the team's lanes i < n.
+// The two orders eigenvalues are ranked in, by counting comparisons:
+// ascending value (the poles of the secular equation) and descending
+// |value| (the column order of U from svd() of a symmetric matrix).
+struct AscendingValue {
+  __device__ static double key(double x) { return x; }
+  __device__ static bool first(double w, double v) { return w < v; }
+};
+struct DescendingAbs {
+  __device__ static double key(double x) { return fabs(x); }
+  __device__ static bool first(double w, double v) { return w > v; }
+};
+// does element k (key w) come before element i (key v)?  Ties by index.
+template <class Order>
+__device__ __forceinline__ int ranks_before(double w, int k, double v, int i) {
+  return Order::first(w, v) || (w == v && k < i);
+}
+// rank of element i among the n elements at(0) .. at(n - 1)
+template <class Order, class At>
+__device__ __forceinline__ int order_rank(int n, int i, At at) {
+  const double v = Order::key(at(i));
+  int rank = 0;
+  for (int k = 0; k < n; ++k) rank += ranks_before<Order>(Order::key(at(k)), k, v, i);
+  return rank;
+}
+
+// Writes perm[rank] = i for the team's lanes i < n, the rank of lane i's
+// eigenvalue (the diagonal of a) by descending |lambda|.
 template <class Team>
 __device__ inline void eig_order(const Team& tm, const double* a, int n, int ld,
                                  int* perm) {
   const int i = tm.lane();
-  if (i < n) {
-    const double li = fabs(a[i * ld + i]);
-    int rank = 0;
-    for (int j = 0; j < n; ++j) {
-      const double lj = fabs(a[j * ld + j]);
-      rank += (lj > li) || (lj == li && j < i);
-    }
-    perm[rank] = i;
-  }
+  if (i < n)
+    perm[order_rank<DescendingAbs>(n, i, [&](int j) { return a[j * ld + j]; })] = i;
   tm.sync();
 }
 

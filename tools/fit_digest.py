@@ -1,8 +1,10 @@
 """Digest of the KL fit's outputs on every fit fixture under tests/golden/,
 for the library named by SCREENFIT_LIB (default: the package's own): one line
 per case, setting and output with the sha256 of the raw bytes of coef, resid,
-w_out and order_out.  Two builds compute the same fit bit for bit exactly
-when their outputs of this tool are equal byte for byte.
+w_out and order_out, and one with the sha256 of the pool of subset bases the
+fit left (Context.fit_pool / fit_pool_wide: masks and entries, sorted by
+mask).  Two builds compute the same fit bit for bit exactly when their outputs
+of this tool are equal byte for byte.
 
     SCREENFIT_LIB=/path/to/libscreenfit.so python tools/fit_digest.py [--out FILE]
 
@@ -15,9 +17,13 @@ two-direction ties, heavy flags, the block sigma of tec / amplitude, and 80,
 wide_tiny96 is no fixture file: it is the input of
 test_wide_phase_fit_tiny_weights, the wide fit's truncated eigen-solve.
 
-Settings, where they apply (<= 60 directions): the default;
+Settings, where they apply: the default; with <= 60 directions
 SF_OPT_FIT_GENERAL = 1 (phase at the case's niter, tec at niter 1, which is
-what the general kernel accepts); SF_OPT_FIT_PACK = 0; SF_OPT_FIT_LEAN = 0.
+what the general kernel accepts; it builds no pool, so its pool line repeats
+the previous fit's), SF_OPT_FIT_PACK = 0, SF_OPT_FIT_LEAN = 0,
+SF_OPT_FIT_SUBSET_DELETION = 0, 2 and 3 (subset bases by Jacobi, by deletions
+from the global basis, by deletions from ancestors at every mask count) and
+SF_OPT_FIT_EIG_WAVES = 1; above 60 directions SF_OPT_FIT_WIDE_CACHE = 0.
 """
 import argparse
 import hashlib
@@ -31,14 +37,22 @@ REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(REPO, "ska-sdp-screen-fitting_amd"))
 from ska_sdp_screen_fitting_amd import geometry, get_context  # noqa: E402
 from ska_sdp_screen_fitting_amd._lib import (  # noqa: E402
-    SF_MAX_DIR, SF_OPT_FIT_GENERAL, SF_OPT_FIT_LEAN, SF_OPT_FIT_PACK,
+    SF_MAX_DIR, SF_OPT_FIT_EIG_WAVES, SF_OPT_FIT_GENERAL, SF_OPT_FIT_LEAN,
+    SF_OPT_FIT_PACK, SF_OPT_FIT_SUBSET_DELETION, SF_OPT_FIT_WIDE_CACHE,
     SF_SCREEN_AMPLITUDE, SF_SCREEN_PHASE, SF_SCREEN_TEC, library_identity)
 from ska_sdp_screen_fitting_amd.stationscreen import station_orders  # noqa: E402
 from ska_sdp_screen_fitting_amd.synthetic import make_solutions  # noqa: E402
 
 GOLDEN = os.path.join(REPO, "tests", "golden")
-SETTINGS = (("default", None), ("general", (SF_OPT_FIT_GENERAL, 1, 0)),
-            ("pack0", (SF_OPT_FIT_PACK, 0, 1)), ("lean0", (SF_OPT_FIT_LEAN, 0, 1)))
+# (tag, (option, value, value restored after the fit), for wide cases)
+SETTINGS = (("default", None, None), ("general", (SF_OPT_FIT_GENERAL, 1, 0), False),
+            ("pack0", (SF_OPT_FIT_PACK, 0, 1), False),
+            ("lean0", (SF_OPT_FIT_LEAN, 0, 1), False),
+            ("deletion0", (SF_OPT_FIT_SUBSET_DELETION, 0, 1), False),
+            ("deletion2", (SF_OPT_FIT_SUBSET_DELETION, 2, 1), False),
+            ("deletion3", (SF_OPT_FIT_SUBSET_DELETION, 3, 1), False),
+            ("eigwaves1", (SF_OPT_FIT_EIG_WAVES, 1, 0), False),
+            ("widecache0", (SF_OPT_FIT_WIDE_CACHE, 0, 1), True))
 
 
 def load(name):
@@ -106,9 +120,9 @@ def main():
         (ctx.set_basis_wide if wide else ctx.set_basis)(pp)
         ph = torch.from_numpy(np.ascontiguousarray(val, np.float64)).to(dev)
         wt = torch.from_numpy(np.ascontiguousarray(weight, np.float32)).to(dev)
-        for tag, opt in SETTINGS:
+        for tag, opt, for_wide in SETTINGS:
             n = niter
-            if opt and wide:
+            if opt and wide != for_wide:
                 continue
             if tag == "general":
                 if screen_type == SF_SCREEN_AMPLITUDE:
@@ -134,6 +148,11 @@ def main():
                 h = hashlib.sha256(np.ascontiguousarray(x.cpu().numpy()).tobytes())
                 lines.append(f"{name} {tag} niter={n} {what} {h.hexdigest()}")
                 print(lines[-1], flush=True)
+            masks, entries = ctx.fit_pool_wide() if wide else ctx.fit_pool()
+            h = hashlib.sha256(np.ascontiguousarray(masks).tobytes())
+            h.update(np.ascontiguousarray(entries).tobytes())
+            lines.append(f"{name} {tag} niter={n} pool[{len(masks)}] {h.hexdigest()}")
+            print(lines[-1], flush=True)
     if args.out:
         os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
         with open(args.out, "w", encoding="utf8") as fh:
