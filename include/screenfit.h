@@ -25,6 +25,11 @@
  *                    calculate_kl_screen at a list of positions instead of
  *                    every pixel (kl_screen.py:411-449) and the Jones terms
  *                    make_matrix forms from it (kl_screen.py:319-378)
+ *   sf_set_tec_freqs / sf_kl_eval_tec <- no counterpart: the reference fits
+ *                    tec soltabs (stationscreen.py:858-1161) but never turns
+ *                    them into phases.  The Jones cube of TEC screens (and a
+ *                    frequency-independent phase screen) at many channels,
+ *                    one contraction per (time, station)
  *
  * Conventions
  *  - Plain C types only.  Return 0 on success, a negative errno-style code
@@ -467,6 +472,53 @@ int sf_kl_eval_sums(sf_ctx* ctx, const double* coef_phase,
  */
 int sf_kl_eval_values(sf_ctx* ctx, const double* coef, int64_t S, float* out,
                       int64_t ring_slots, unsigned flags);
+
+/*
+ * Jones cubes of TEC screens at many channels (kl_tec.hip).  The phase of a
+ * TEC screen at frequency nu is rad_per_tecu * dTEC with rad_per_tecu =
+ * tec_to_phase / nu, so the F channels of one (time, station) share one
+ * contraction and differ in the epilogue only.
+ */
+#define SF_MAX_TEC_FREQ 4096
+/* Bind the F output channels (host arrays): channel f takes its screens from
+ * TEC frequency tec_index[f] in 0..F_tec-1 (NULL = 0 for every f) and
+ * multiplies them by rad_per_tecu[f].  F_tec is the frequency extent of the
+ * coefficient arrays sf_kl_eval_tec will be given.  Synchronises, like
+ * sf_set_points.  The binding lives until the next sf_set_tec_freqs or
+ * sf_destroy; it does not depend on the geometry, so sf_set_basis* and
+ * sf_set_piercepoints do not drop it.  SF_EINVAL for F outside
+ * 1..SF_MAX_TEC_FREQ, F_tec < 1, an index out of range, a non-finite scale or
+ * a NULL scale pointer; a failed call keeps the previous binding. */
+int sf_set_tec_freqs(sf_ctx* ctx, const double* rad_per_tecu_host,
+                     const int* tec_index_host, int F, int F_tec);
+/*
+ * Device inputs: tec_coef [T][F_tec][A][D] float64 in TECU (the layout of
+ * "tec_screen000"); phase_coef NULL or the same shape in radians, the
+ * frequency-independent phase screens of a tecandphase solution.  Device
+ * output: out [T][F][A][4][ny][nx] float32, the FITS a-term layout, planes as
+ * sf_kl_eval:
+ *   out[t][f][a][.][p] = (cos, sin, cos, sin)(
+ *       rad_per_tecu[f] * sum_d Cpix[p][d] * tec[t][i_f][a][d]
+ *                       + sum_d Cpix[p][d] * ph[t][i_f][a][d] ),  i_f = tec_index[f].
+ * Both contractions are float64 and run once per (t, TEC frequency, a); the
+ * scale is applied to the contracted value, one float64 multiply in turns,
+ * and the reduction in revolutions is exact (as sf_kl_eval with
+ * SF_EVAL_FAST_SINCOS; without the flag, fp64 sincos).  Needs sf_set_grid on
+ * the geometry of sf_set_basis, sf_set_basis_wide or sf_set_piercepoints, and
+ * sf_set_tec_freqs (else SF_EINVAL, the message names the missing call); one
+ * kernel serves 1 <= D <= SF_MAX_EVAL_DIR.  T * A < 2^31.
+ * flags: SF_EVAL_NAN_SCRUB, SF_EVAL_FAST_SINCOS, SF_EVAL_NT_STORES (honoured
+ * for 16-byte-aligned output and nx * ny % 4 == 0), SF_EVAL_BIG_ENDIAN; any
+ * other bit is SF_EINVAL.  The output needs 4-byte alignment only.  A NaN
+ * coefficient gives NaN planes in all F channels of its own (t, a) -- those of
+ * its TEC frequency -- and nowhere else; with the scrub they are 1 / 0.  A TEC
+ * frequency that no channel refers to is never read.  No ring and no
+ * checksums.  SF_OPT_EVAL_MAX_BLOCKS, _GROUPS, _BANDS and _XCD_MAP are
+ * honoured.  Enqueued on the context stream (one launch per TEC frequency that
+ * has channels); does not synchronise.
+ */
+int sf_kl_eval_tec(sf_ctx* ctx, const double* tec_coef, const double* phase_coef,
+                   int64_t T, int A, float* out, unsigned flags);
 
 /*
  * Screens sampled at positions (kl_points.hip): the value

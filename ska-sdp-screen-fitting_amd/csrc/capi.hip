@@ -1,6 +1,7 @@
 // capi.hip -- the extern "C" boundary of libscreenfit (include/screenfit.h).
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cmath>
 #include <cstring>
 #include <string>
@@ -156,6 +157,7 @@ int sf_destroy(sf_ctx* ctx) {
   hipFree(ctx->d_gw);
   hipFree(ctx->d_smooth);
   hipFree(ctx->d_tess_tab);
+  hipFree(ctx->d_tec_ch);
   hipFree(ctx->d_trash);
   delete ctx;
   return SF_OK;
@@ -796,6 +798,87 @@ int sf_kl_eval_values(sf_ctx* ctx, const double* coef, int64_t S, float* out,
   if (S == 0) return SF_OK;
   SF_HIP(hipSetDevice(ctx->device));
   return sf::launch_eval_values(ctx, coef, S, out, ring, flags);
+}
+
+int sf_set_tec_freqs(sf_ctx* ctx, const double* rad_per_tecu, const int* tec_index,
+                     int F, int F_tec) {
+  SF_REQUIRE(ctx, SF_EINVAL, "sf_set_tec_freqs: NULL context");
+  SF_REQUIRE(rad_per_tecu, SF_EINVAL, "sf_set_tec_freqs: NULL scales");
+  SF_REQUIRE(F >= 1 && F <= SF_MAX_TEC_FREQ, SF_EINVAL,
+             "sf_set_tec_freqs: F out of range [1, SF_MAX_TEC_FREQ]");
+  SF_REQUIRE(F_tec >= 1, SF_EINVAL, "sf_set_tec_freqs: F_tec must be >= 1");
+  for (int f = 0; f < F; ++f) {
+    SF_REQUIRE(std::isfinite(rad_per_tecu[f]), SF_EINVAL,
+               "sf_set_tec_freqs: non-finite scale");
+    SF_REQUIRE(!tec_index || (tec_index[f] >= 0 && tec_index[f] < F_tec), SF_EINVAL,
+               "sf_set_tec_freqs: TEC frequency index out of range [0, F_tec)");
+  }
+  // the channel lists, grouped by TEC frequency, a frequency's channels in
+  // ascending order; only frequencies that some channel refers to take room
+  // (F_tec itself is unbounded)
+  std::vector<double> k(F);
+  std::vector<int> ch(F), order(F);
+  for (int f = 0; f < F; ++f) order[f] = f;
+  std::stable_sort(order.begin(), order.end(), [&](int a, int b) {
+    return (tec_index ? tec_index[a] : 0) < (tec_index ? tec_index[b] : 0);
+  });
+  std::vector<int> used, off(1, 0);  // used[j]: the j-th TEC frequency with channels
+  for (int c = 0; c < F; ++c) {
+    const int f = order[c], i = tec_index ? tec_index[f] : 0;
+    if (used.empty() || used.back() != i) {
+      if (!used.empty()) off.push_back(c);
+      used.push_back(i);
+    }
+    k[c] = rad_per_tecu[f] / 6.283185307179586;  // turns per TECU
+    ch[c] = f;
+  }
+  off.push_back(F);
+  SF_HIP(hipSetDevice(ctx->device));
+  // queued evaluations may still read the previous lists
+  SF_HIP(hipStreamSynchronize(ctx->stream));
+  // the new buffer first: a failure keeps the previous binding
+  double* d = nullptr;
+  const size_t bytes = (size_t)F * (sizeof(double) + sizeof(int));
+  if (hipMalloc(reinterpret_cast<void**>(&d), bytes) != hipSuccess) {
+    set_error("sf_set_tec_freqs: hipMalloc failed");
+    return SF_ENOMEM;
+  }
+  if (hipMemcpy(d, k.data(), F * sizeof(double), hipMemcpyHostToDevice) != hipSuccess ||
+      hipMemcpy(d + F, ch.data(), F * sizeof(int), hipMemcpyHostToDevice) != hipSuccess) {
+    (void)hipFree(d);
+    set_error("sf_set_tec_freqs: copy of the channel lists failed");
+    return SF_EIO;
+  }
+  (void)hipFree(ctx->d_tec_ch);
+  ctx->d_tec_ch = d;
+  ctx->tec_F = F;
+  ctx->tec_F_tec = F_tec;
+  ctx->tec_used.swap(used);
+  ctx->tec_off.swap(off);
+  return SF_OK;
+}
+
+int sf_kl_eval_tec(sf_ctx* ctx, const double* tec_coef, const double* phase_coef,
+                   int64_t T, int A, float* out, unsigned flags) {
+  SF_REQUIRE(ctx, SF_EINVAL, "sf_kl_eval_tec: NULL context");
+  SF_REQUIRE(ctx->D > 0 && ctx->n_pix > 0 && ctx->d_cfrag, SF_EINVAL,
+             "sf_kl_eval_tec: call sf_set_grid first");
+  SF_REQUIRE(ctx->tec_F > 0 && ctx->d_tec_ch, SF_EINVAL,
+             "sf_kl_eval_tec: call sf_set_tec_freqs first");
+  SF_REQUIRE(tec_coef && out && T >= 0 && A >= 1, SF_EINVAL,
+             "sf_kl_eval_tec: bad argument");
+  SF_REQUIRE(T * A <= INT32_MAX, SF_EINVAL,
+             "sf_kl_eval_tec: T * A too large for one call (split the time axis)");
+  SF_REQUIRE((reinterpret_cast<uintptr_t>(out) & 3) == 0, SF_EINVAL,
+             "sf_kl_eval_tec: output not 4-byte aligned");
+  SF_REQUIRE((flags & ~(SF_EVAL_NAN_SCRUB | SF_EVAL_FAST_SINCOS | SF_EVAL_NT_STORES |
+                        SF_EVAL_BIG_ENDIAN)) == 0,
+             SF_EINVAL,
+             "sf_kl_eval_tec: flags other than SF_EVAL_NAN_SCRUB, SF_EVAL_FAST_SINCOS, "
+             "SF_EVAL_NT_STORES and SF_EVAL_BIG_ENDIAN");
+  if (T == 0) return SF_OK;
+  SF_HIP(hipSetDevice(ctx->device));
+  return sf::launch_eval_tec(ctx, tec_coef, phase_coef, T, A, out, flags);
 }
 
 // scipy.ndimage._gaussian_kernel1d(sigma, 0, int(4 sigma + 0.5)) uploaded to

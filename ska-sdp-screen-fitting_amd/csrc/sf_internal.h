@@ -5,6 +5,7 @@
 
 #include <cstdint>
 #include <string>
+#include <vector>
 
 #include "screenfit.h"
 
@@ -185,6 +186,14 @@ struct sf_ctx {
   int pt_cus = 0;              // compute units of the device
   double* d_pxy = nullptr;     // [P][2]
   double* d_pfrag = nullptr;   // [pt_tiles][pt_ks_pad][64] MFMA B fragments
+  // output channels of sf_kl_eval_tec (sf_set_tec_freqs, kl_tec.hip), grouped
+  // by TEC frequency; independent of the geometry
+  int tec_F = 0;               // channels bound (0: none)
+  int tec_F_tec = 0;           // TEC frequencies of the coefficient arrays
+  std::vector<int> tec_used;   // the TEC frequencies that have channels, ascending
+  std::vector<int> tec_off;    // [used + 1] their ranges in the lists
+  double* d_tec_ch = nullptr;  // [F] scale in turns per TECU, then [F] int
+                               // channel index, both in list order
   // fit scratch
   uint8_t* d_skip = nullptr;   // [F][A] block skip flags
   size_t skip_cap = 0;
@@ -304,6 +313,9 @@ int launch_eval_wide(sf_ctx* ctx, const double* coef, const double* cxx,
 // screen values on the pixel grid, any D (kl_values.hip)
 int launch_eval_values(sf_ctx* ctx, const double* coef, int64_t S, float* out,
                        int64_t ring, unsigned flags);
+// Jones cubes of TEC screens at the bound channels, any D (kl_tec.hip)
+int launch_eval_tec(sf_ctx* ctx, const double* tec, const double* phase, int64_t T,
+                    int A, float* out, unsigned flags);
 // screen positions (kl_points.hip): padded shapes of the point basis, its
 // kernel (d_pxy -> d_pfrag) and the slot-major evaluation at the points
 int points_ks_pad(int D);

@@ -25,6 +25,7 @@ SF_MAX_DIR = 60        # directions per slot of set_basis / fit
 SF_MAX_FIT_DIR = 128   # ... of set_basis_wide / fit after it
 SF_MAX_EVAL_DIR = 128  # ... of set_piercepoints, set_grid, eval*, tess_fill
 SF_MAX_POINTS = 4096   # positions of set_points
+SF_MAX_TEC_FREQ = 4096  # output channels of set_tec_freqs
 SF_OPT_FIT_GENERAL = 1
 SF_OPT_EVAL_KERNEL = 2
 SF_OPT_EVAL_MAX_BLOCKS = 3
@@ -77,6 +78,7 @@ EXPORTED = (
     "sf_tess_fill", "sf_smooth",
     "sf_set_points", "sf_kl_eval_points", "sf_kl_eval_point_values",
     "sf_kl_eval_values",
+    "sf_set_tec_freqs", "sf_kl_eval_tec",
 )
 
 
@@ -169,6 +171,8 @@ def load_library(path=None):
             "sf_kl_eval_points": ([vp, vp, vp, vp, i64, vp, ctypes.c_uint], c_int),
             "sf_kl_eval_point_values": ([vp, vp, i64, vp], c_int),
             "sf_kl_eval_values": ([vp, vp, i64, vp, i64, ctypes.c_uint], c_int),
+            "sf_set_tec_freqs": ([vp, vp, vp, c_int, c_int], c_int),
+            "sf_kl_eval_tec": ([vp, vp, vp, i64, c_int, vp, ctypes.c_uint], c_int),
         }
         for name, (args, res) in sig.items():
             fn = getattr(lib, name)
@@ -225,6 +229,7 @@ class Context:
         self.D = 0
         self.grid = None
         self.points = 0  # positions bound by set_points
+        self.tec_freqs = None  # (F, F_tec) bound by set_tec_freqs
         self.options = {}  # sf_set_option values set through this object
 
     def close(self):
@@ -422,6 +427,42 @@ class Context:
             self.h, self._dev(coef, np.float64, int(S) * self.D, "coef"), int(S),
             self._dev(out, np.float32, self._out_numel(S, ring) // 4, "out"), ring,
             int(flags)), "sf_kl_eval_values")
+
+    def set_tec_freqs(self, rad_per_tecu, tec_index=None, n_tec_freq=None):
+        """sf_set_tec_freqs: bind the F output channels of ``eval_tec``.
+        Channel f renders ``rad_per_tecu[f]`` (= tec_to_phase / nu_f) times the
+        screens of TEC frequency ``tec_index[f]`` (default: 0 for every f) of
+        coefficient arrays with ``n_tec_freq`` frequencies (default: 1 without
+        ``tec_index``, else its largest entry + 1).  The binding survives a
+        change of geometry; a failed call keeps the previous one."""
+        k = np.ascontiguousarray(rad_per_tecu, dtype=np.float64).reshape(-1)
+        idx = None
+        if tec_index is not None:
+            idx = np.ascontiguousarray(tec_index, dtype=np.int32).reshape(-1)
+            if idx.shape != k.shape:
+                raise ValueError(f"tec_index: shape {idx.shape}, expected {k.shape}")
+        if n_tec_freq is None:
+            n_tec_freq = 1 if idx is None or idx.size == 0 else int(idx.max()) + 1
+        _check(self.lib.sf_set_tec_freqs(
+            self.h, k.ctypes.data, None if idx is None else idx.ctypes.data,
+            k.size, int(n_tec_freq)), "sf_set_tec_freqs")
+        self.tec_freqs = (int(k.size), int(n_tec_freq))
+
+    def eval_tec(self, tec_coef, T, A, out, phase_coef=None,
+                 flags=SF_EVAL_NAN_SCRUB | SF_EVAL_FAST_SINCOS | SF_EVAL_NT_STORES):
+        """sf_kl_eval_tec: Jones planes [T, F, A, 4, ny, nx] float32 of the TEC
+        screens ``tec_coef`` [T, F_tec, A, D] (TECU) at the channels of
+        ``set_tec_freqs``, plus the frequency-independent phase screens
+        ``phase_coef`` (same shape, radians) when given: one contraction per
+        (time, TEC frequency, station), the epilogue per channel."""
+        F, F_tec = self.tec_freqs if self.tec_freqs else (0, 0)
+        nx, ny = self.grid if self.grid else (0, 0)
+        n = int(T) * F_tec * int(A) * self.D
+        _check(self.lib.sf_kl_eval_tec(
+            self.h, self._dev(tec_coef, np.float64, n, "tec_coef"),
+            self._dev(phase_coef, np.float64, n, "phase_coef"), int(T), int(A),
+            self._dev(out, np.float32, int(T) * F * int(A) * 4 * nx * ny, "out"),
+            int(flags)), "sf_kl_eval_tec")
 
     def set_points(self, xy):
         """sf_set_points: P screen positions ``xy`` [P, 2] (x, y in

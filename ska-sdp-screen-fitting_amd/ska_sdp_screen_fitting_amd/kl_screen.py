@@ -41,6 +41,26 @@ def read_patch_names(skymodel_filename):
     return names
 
 
+def tec_channel_groups(tec_index, n_tec_freq):
+    """The launches of ``sf_kl_eval_tec`` for the channel binding
+    ``tec_index`` [F] over ``n_tec_freq`` TEC frequencies: a list of
+    ``(i, channels)``, one entry per TEC frequency i that some channel refers
+    to, in ascending i, ``channels`` the int array of its output channels in
+    ascending order.  A frequency without channels has no entry: its
+    coefficients are never read.  Raises ValueError for an index outside
+    ``0..n_tec_freq-1`` (the C side's SF_EINVAL)."""
+    idx = np.asarray(tec_index, np.int64).reshape(-1)
+    if int(n_tec_freq) < 1:
+        raise ValueError(f"n_tec_freq: {n_tec_freq}, expected >= 1")
+    if idx.size and (idx.min() < 0 or idx.max() >= int(n_tec_freq)):
+        raise ValueError(f"tec_index: values {idx.min()}..{idx.max()} outside "
+                         f"0..{int(n_tec_freq) - 1}")
+    order = np.argsort(idx, kind="stable")
+    used, start = np.unique(idx[order], return_index=True)
+    return [(int(i), order[a:b]) for i, a, b in
+            zip(used, start, list(start[1:]) + [idx.size])]
+
+
 class KLEvaluator:
     """Device state for evaluating KL screens on one grid and / or at a list
     of positions.  Owns its sf_ctx: the basis, pixel grid and points it sets
@@ -163,6 +183,63 @@ class KLEvaluator:
         lead = coef.shape[:-1]
         out = self.values_device(self._upload(coef), flags=flags)
         return out.cpu().numpy().reshape(lead + (self.ny, self.nx))
+
+    def eval_tec_device(self, tec_dev, rad_per_tecu, tec_index=None, phase_dev=None,
+                        out_dev=None, flags=DEFAULT_FLAGS):
+        """TEC screens to Jones planes at F channels (``sf_kl_eval_tec``):
+        ``tec_dev`` device [T, F_tec, A, D] float64 in TECU, ``rad_per_tecu``
+        [F] (= tec_to_phase / nu), ``tec_index`` [F] the TEC frequency each
+        channel takes (default: 0, for F_tec = 1), ``phase_dev`` None or the
+        frequency-independent phase screens in radians, shaped as ``tec_dev``
+        -> device [T, F, A, 4, ny, nx] float32 of the phase
+        ``rad_per_tecu[f] * dTEC + phi0``.  One contraction per (time, TEC
+        frequency, station); no coefficients are replicated per channel."""
+        torch = self.torch
+        if tec_dev.dim() != 4 or tec_dev.shape[3] != self.D:
+            raise ValueError(f"tec_dev: shape {tuple(tec_dev.shape)}, expected "
+                             f"(T, F_tec, A, {self.D})")
+        T, F_tec, A, _ = tec_dev.shape
+        k = np.asarray(rad_per_tecu, np.float64).reshape(-1)
+        if tec_index is None:
+            if F_tec != 1:
+                raise ValueError("tec_index: needed for more than one tec frequency")
+        else:
+            tec_channel_groups(tec_index, F_tec)  # range check
+        if phase_dev is not None and phase_dev.shape != tec_dev.shape:
+            raise ValueError(f"phase_dev: shape {tuple(phase_dev.shape)}, expected "
+                             f"{tuple(tec_dev.shape)}")
+        if out_dev is None:
+            out_dev = torch.empty((T, k.size, A, 4, self.ny, self.nx),
+                                  dtype=torch.float32, device=self.dev)
+        with torch.cuda.device(self.dev):
+            self.ctx.set_stream(torch.cuda.current_stream(self.dev).cuda_stream)
+            self._bind_tec_freqs(k, tec_index, F_tec)
+            self.ctx.eval_tec(tec_dev, T, A, out_dev, phase_dev, flags)
+        return out_dev
+
+    def _bind_tec_freqs(self, k, tec_index, F_tec):
+        """sf_set_tec_freqs unless this binding is the context's already (it
+        synchronises: a write's batches share one binding)."""
+        idx = None if tec_index is None else np.asarray(tec_index, np.int32).reshape(-1)
+        key = (k.tobytes(), None if idx is None else idx.tobytes(), int(F_tec))
+        if getattr(self, "_tec_key", None) != key:
+            self._tec_key = None
+            self.ctx.set_tec_freqs(k, idx, F_tec)
+            self._tec_key = key
+
+    def eval_tec_host(self, tec_coef, rad_per_tecu, tec_index=None, phase_coef=None,
+                      flags=DEFAULT_FLAGS):
+        """Host [T, F_tec, A, D] TEC (and optional phase) coefficients -> host
+        float32 [T, F, A, 4, ny, nx] (``eval_tec_device``)."""
+        torch = self.torch
+
+        def up(a):
+            return torch.from_numpy(np.ascontiguousarray(a, np.float64)).to(self.dev)
+
+        out = self.eval_tec_device(up(tec_coef), rad_per_tecu, tec_index,
+                                   None if phase_coef is None else up(phase_coef),
+                                   flags=flags)
+        return out.cpu().numpy()
 
     def smooth_device(self, out_dev, smooth_pix, flags):
         """Screen.write's Gaussian (screen.py:353-362) in place on a device

@@ -11,8 +11,15 @@ that renders them) and writes either
   ``sf_kl_eval_values`` (csrc/kl_values.hip): fp64 contraction, one cast; or
 * ``aterm_type="gain"``: the ordinary 6-axis Jones cube at given frequencies.
   The KL map is linear, so the phase screen at frequency nu is the screen of
-  the coefficients ``tec_coef * tec_to_phase / nu``: one broadcast on the
-  device, then ``sf_kl_eval``.
+  the coefficients ``tec_coef * tec_to_phase / nu``.  Two paths render it
+  (keyword ``fused``): the replicated one -- one broadcast on the device, then
+  ``sf_kl_eval`` over T x F x A slots -- and the fused one, ``sf_kl_eval_tec``
+  (csrc/kl_tec.hip): one contraction per (time, station), the scale and the
+  cos / sin per channel, no per-channel coefficients on the device.
+
+With ``phase_soltab_name`` (LOFAR-style ``tecandphase`` solutions: a tec soltab
+and a frequency-independent scalar-phase soltab over the same directions) the
+gain cube renders ``exp(i (phi0 + tec_to_phase * dTEC / nu))``.
 """
 
 import multiprocessing
@@ -56,17 +63,76 @@ def tec_to_phase_coef(tec_coef, freqs_hz, tec_to_phase=TEC_TO_PHASE,
     return (src * (tec_to_phase / nu)[None, :, None, None]).contiguous()
 
 
+# fused="auto": the (D, F) region where sf_kl_eval_tec beat tec_to_phase_coef +
+# sf_kl_eval by more than the latter's max - min spread, measured by
+# tools/eval_tec.py at 256^2 (profiles/eval_tec.txt: D in {20, 50, 61, 80, 128}
+# x F in {1, 8, 32}).  It won every shape above 60 directions, where sf_kl_eval
+# runs the fp64 wide kernel (x1.04-1.05 at F = 1, x1.3-2.3 at F = 8 and 32),
+# and none at D = 20 and 50, where the LDS-staged and integer-digit kernels of
+# sf_kl_eval stay ahead or level.  Between measured points the rule takes the
+# nearest measured point at or below in both D and F; below the smallest
+# measured D or F it is the replicated path.
+FUSED_AUTO_D = (20, 50, 61, 80, 128)
+FUSED_AUTO_F = (1, 8, 32)
+# FUSED_AUTO_WINS[i][j]: fused won at D = FUSED_AUTO_D[i], F = FUSED_AUTO_F[j]
+FUSED_AUTO_WINS = ((False, False, False),
+                   (False, False, False),
+                   (True, True, True),
+                   (True, True, True),
+                   (True, True, True))
+
+
+def fused_auto(n_dir, n_freq):
+    """The ``fused="auto"`` rule: True where the measured table says the fused
+    evaluation wins for ``n_dir`` directions and ``n_freq`` output channels."""
+    i = int(np.searchsorted(FUSED_AUTO_D, n_dir, side="right")) - 1
+    j = int(np.searchsorted(FUSED_AUTO_F, n_freq, side="right")) - 1
+    return i >= 0 and j >= 0 and FUSED_AUTO_WINS[i][j]
+
+
+def check_phase_soltab_axes(soltab_tec, soltab_phase):
+    """The phase soltab of a tecandphase solution must lie on the tec soltab's
+    grid: axes time, freq, ant, dir (no pol), the tec soltab's times, stations
+    and directions, and its frequencies or a single one.  Raises ValueError
+    naming the axis that differs; returns True when the phase soltab's
+    length-1 frequency axis has to be broadcast over the tec soltab's."""
+    names = list(soltab_phase.get_axes_names())
+    if sorted(names) != ["ant", "dir", "freq", "time"]:
+        raise ValueError(f"phase soltab: axes {names}, expected time, freq, ant "
+                         "and dir (a scalar phase, no pol axis)")
+    for axis in ("time", "ant", "dir"):
+        a, b = np.asarray(getattr(soltab_tec, axis)), np.asarray(getattr(soltab_phase, axis))
+        same = a.shape == b.shape and (
+            np.array_equal(a, b) if axis == "time" else
+            [str(x) for x in a] == [str(x) for x in b])
+        if not same:
+            raise ValueError(f"phase soltab: its {axis} axis differs from the tec "
+                             f"soltab's ({b.shape[0]} against {a.shape[0]} entries"
+                             f"{'' if a.shape != b.shape else ', other values'})")
+    fa, fb = np.asarray(soltab_tec.freq, np.float64), np.asarray(soltab_phase.freq, np.float64)
+    if np.array_equal(fa, fb):
+        return False
+    if fb.shape == (1,):
+        return True
+    raise ValueError("phase soltab: its freq axis differs from the tec soltab's "
+                     f"({fb.shape[0]} against {fa.shape[0]} entries) and is not of "
+                     "length 1")
+
+
 class KLTecScreen(Screen):
     """KL screens of a ``tec`` soltab (values in TECU)."""
 
     def __init__(self, name, h5parm_filename, skymodel_filename, rad, dec,
                  width_ra, width_dec, solset_name="sol000",
-                 tec_soltab_name="tec000"):
+                 tec_soltab_name="tec000", phase_soltab_name=None):
         super().__init__(name, h5parm_filename, skymodel_filename, rad, dec,
                          width_ra, width_dec, solset_name=solset_name,
                          phase_soltab_name=tec_soltab_name,
                          amplitude_soltab_name=None)
         self.input_tec_soltab_name = tec_soltab_name
+        # the frequency-independent scalar phase of a tecandphase solution
+        self.input_phi0_soltab_name = phase_soltab_name
+        self.vals_phi0 = None  # its screens on tec_screen000's axes, radians
         self.height = None
         self.beta_val = None
         self.r_0 = None
@@ -78,8 +144,11 @@ class KLTecScreen(Screen):
 
     def fit(self):
         """Fit the tec screens as ``KLScreen.fit`` fits phases: reference
-        station among the first 10, order min(20, D - 1) scaled per station."""
+        station among the first 10, order min(20, D - 1) scaled per station.
+        With a phase soltab, its screens too, same reference station and
+        order rule (``phase_screen000``)."""
         self._evaluators = {}
+        self.vals_phi0 = None
         h5 = H5parm(self.input_h5parm_filename)
         solset = h5.get_solset(self.input_solset_name)
         soltab_tec = solset.get_soltab(self.input_tec_soltab_name)
@@ -97,6 +166,19 @@ class KLTecScreen(Screen):
         if rc != 0:
             raise ValueError(f"soltab {self.input_tec_soltab_name!r} of type "
                              f"{soltab_tec.get_type()!r} cannot be fitted")
+        if self.input_phi0_soltab_name is not None:
+            soltab_phi0 = solset.get_soltab(self.input_phi0_soltab_name)
+            if soltab_phi0.get_type() != "phase":
+                raise ValueError(f"soltab {self.input_phi0_soltab_name!r} of type "
+                                 f"{soltab_phi0.get_type()!r} is not a phase soltab")
+            broadcast = check_phase_soltab_axes(soltab_tec, soltab_phi0)
+            stationscreen.run(soltab_phi0, "phase_screen000", order=screen_order,
+                              ref_ant=ref_ind, scale_order=True, adjust_order=True,
+                              ncpu=self.ncpu or 0, device=self.device)
+            phi0 = np.asarray(solset.get_soltab("phase_screen000").val, np.float64)
+            if broadcast:
+                phi0 = np.repeat(phi0, len(soltab_tec.freq), axis=1)
+            self.vals_phi0 = phi0
         st = solset.get_soltab("tec_screen000")
         # (vals_ph / times_ph / freqs_ph: the names Screen.write's chunking reads)
         self.vals_ph = st.val
@@ -181,15 +263,26 @@ class KLTecScreen(Screen):
             pipe.close()
 
     def write_chunk_gain(self, writer, g_start, g_stop, cellsize_deg, freqs_hz,
-                         tec_to_phase, max_batch_bytes=1 << 30):
+                         tec_to_phase, max_batch_bytes=1 << 30, fused="auto"):
         """Jones planes (cos, sin, cos, sin) of the phase tec_to_phase / nu x
-        dTEC at ``freqs_hz``, times [g_start, g_stop)."""
+        dTEC (+ the phase soltab's screens, when the object has one) at
+        ``freqs_hz``, times [g_start, g_stop).
+
+        ``fused=False``: the coefficients replicated and scaled per channel
+        (``tec_to_phase_coef``, plus the phase coefficients: the KL map is
+        linear and the piercepoints are shared), then ``sf_kl_eval``.
+        ``fused=True``: the TEC (and phase) coefficients uploaded once,
+        ``sf_kl_eval_tec`` per batch.  ``"auto"``: ``fused_auto(D, F)``."""
         from .streaming import PinnedPipeline
         torch = __import__("torch")
+        if fused not in (False, True, "auto"):
+            raise ValueError(f'fused: {fused!r}, expected False, True or "auto"')
         ev = self.evaluator(cellsize_deg)
         vals = np.asarray(self.vals_ph)
         n_a, D = vals.shape[2], vals.shape[3]
         n_f = len(freqs_hz)
+        if fused == "auto":
+            fused = fused_auto(D, n_f)
         fidx = (np.zeros(n_f, int) if vals.shape[1] == 1 else
                 nearest_index(self.freqs_ph, freqs_hz))
         per_slot = 16 * ev.nx * ev.ny
@@ -198,23 +291,36 @@ class KLTecScreen(Screen):
         rows = min(rows, g_stop - g_start)
         tec = torch.from_numpy(np.ascontiguousarray(vals[g_start:g_stop],
                                                     np.float64)).to(ev.dev)
+        phi0 = None
+        if self.vals_phi0 is not None:
+            phi0 = torch.from_numpy(np.ascontiguousarray(
+                self.vals_phi0[g_start:g_stop], np.float64)).to(ev.dev)
         pipe = PinnedPipeline(torch, ev.dev, rows * row_bytes)
         flags = DEFAULT_FLAGS | SF_EVAL_NAN_SCRUB | SF_EVAL_BIG_ENDIAN
+        rad_per_tecu = tec_to_phase / np.asarray(freqs_hz, np.float64)
+        idx = torch.as_tensor(np.asarray(fidx, np.int64), device=ev.dev)
         try:
             for t0 in range(g_start, g_stop, rows):
                 t1 = min(g_stop, t0 + rows)
                 n = (t1 - t0) * n_f * n_a
-                coef = tec_to_phase_coef(tec[t0 - g_start:t1 - g_start], freqs_hz,
-                                         tec_to_phase, fidx).view(n, D)
+                sl = slice(t0 - g_start, t1 - g_start)
                 slot, buf = pipe.device_buffer(n * per_slot)
-                out = buf.view(torch.float32).view(n, 4, ev.ny, ev.nx)
-                ev.eval_device(coef, out, flags)
+                if fused:
+                    out = buf.view(torch.float32).view(t1 - t0, n_f, n_a, 4, ev.ny, ev.nx)
+                    ev.eval_tec_device(tec[sl], rad_per_tecu, fidx,
+                                       None if phi0 is None else phi0[sl], out, flags)
+                else:
+                    coef = tec_to_phase_coef(tec[sl], freqs_hz, tec_to_phase, fidx)
+                    if phi0 is not None:
+                        coef = coef + phi0[sl].index_select(1, idx)
+                    out = buf.view(torch.float32).view(n, 4, ev.ny, ev.nx)
+                    ev.eval_device(coef.view(n, D), out, flags)
                 pipe.submit(slot, n * per_slot, writer)
         finally:
             pipe.close()
 
     def write(self, out_dir, cellsize_deg, aterm_type="tec",
-              tec_to_phase=TEC_TO_PHASE, freqs_hz=None, ncpu=0):
+              tec_to_phase=TEC_TO_PHASE, freqs_hz=None, ncpu=0, fused="auto"):
         """Write ``{name}_{g}.fits`` per time chunk (Screen.write's gap and
         memory chunking) and ``{name}.txt`` listing them.
 
@@ -224,7 +330,10 @@ class KLTecScreen(Screen):
         x dTEC / nu; with several tec frequencies each output frequency takes
         the nearest one's screens.  ``tec_to_phase`` (rad Hz / TECU) is the
         imager-side convention, not something the reference defines: check it
-        against the consumer of the cube."""
+        against the consumer of the cube.  With a phase soltab the gain cube
+        renders phi0 + tec_to_phase x dTEC / nu; ``aterm_type="tec"`` ignores
+        it.  ``fused`` (``False``, ``True`` or ``"auto"``) picks the gain
+        cube's evaluation, see ``write_chunk_gain``."""
         if aterm_type not in ("tec", "gain"):
             raise ValueError(f"unknown aterm_type {aterm_type!r}")
         self.ncpu = ncpu
@@ -247,7 +356,7 @@ class KLTecScreen(Screen):
             try:
                 if gain:
                     self.write_chunk_gain(writer, g_start, g_stop, cellsize_deg,
-                                          freqs, tec_to_phase)
+                                          freqs, tec_to_phase, fused=fused)
                 else:
                     self.write_chunk(writer, g_start, g_stop, cellsize_deg)
             finally:
@@ -264,11 +373,14 @@ def make_tec_aterm_image(h5parmfile, soltabname="tec000", outroot="",
                          bounds_deg=None, bounds_mid_deg=None, skymodel=None,
                          solsetname="sol000", padding_fraction=1.4,
                          cellsize_deg=0.2, aterm_type="tec", ncpu=0,
-                         tec_to_phase=TEC_TO_PHASE, freqs_hz=None):
+                         tec_to_phase=TEC_TO_PHASE, freqs_hz=None, fused="auto",
+                         phase_soltab_name=None):
     """``make_aterm_image`` for a tec soltab: fit KL screens to it and write
     the dTEC cube (``aterm_type="tec"``) or the Jones cube at ``freqs_hz``
-    (``"gain"``, see ``KLTecScreen.write`` for ``tec_to_phase``).  Bounds and
-    padding as ``make_aterm_image``.  Returns None."""
+    (``"gain"``, see ``KLTecScreen.write`` for ``tec_to_phase`` and ``fused``).
+    ``phase_soltab_name``: the scalar-phase soltab of a tecandphase solution,
+    added to the gain cube's phase.  Bounds and padding as
+    ``make_aterm_image``.  Returns None."""
     if isinstance(bounds_deg, str):
         bounds_deg = [float(f.strip()) for f in bounds_deg.strip("[]").split(";")]
     if isinstance(bounds_mid_deg, str):
@@ -286,7 +398,8 @@ def make_tec_aterm_image(h5parmfile, soltabname="tec000", outroot="",
     width_deg = bounds_deg[3] - bounds_deg[1]
     screen = KLTecScreen(os.path.basename(outroot), h5parmfile, skymodel,
                          bounds_mid_deg[0], bounds_mid_deg[1], width_deg, width_deg,
-                         solset_name=solsetname, tec_soltab_name=soltabname)
+                         solset_name=solsetname, tec_soltab_name=soltabname,
+                         phase_soltab_name=phase_soltab_name)
     screen.process(ncpu=ncpu)
     screen.write(os.path.dirname(outroot), cellsize_deg, aterm_type=aterm_type,
-                 tec_to_phase=tec_to_phase, freqs_hz=freqs_hz, ncpu=ncpu)
+                 tec_to_phase=tec_to_phase, freqs_hz=freqs_hz, ncpu=ncpu, fused=fused)
