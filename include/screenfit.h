@@ -96,7 +96,8 @@ typedef struct sf_ctx sf_ctx;
 /* Operator parameters of stationscreen.run (stationscreen.py:858-871). */
 typedef struct sf_fit_params {
   int screen_type;  /* SF_SCREEN_PHASE, _TEC or _AMPLITUDE */
-  int niter;        /* outlier-flagging iterations (phase: 2) */
+  int niter;        /* outlier-flagging iterations (phase: 2), 1..64: anything
+                       else is SF_EINVAL */
   double nsigma;    /* outlier threshold in circular sigmas (5.0) */
   int adjust_order; /* adapt the order toward reduced chi^2 ~ 1 (1) */
   int ref_ant;      /* GLOBAL reference station index, -1 = none */

@@ -49,14 +49,16 @@ def test_reference_station(golden):
     assert okl.reference_station(golden["weight"]) == int(golden["ref_ant"])
 
 
-def ill_conditioned_slots(g):
+def ill_conditioned_slots(g, r_0=100.0, beta=5.0 / 3.0):
     """Slots whose final fit takes atan2 of near-zero values (the reference is
-    chaotic there: its own output changes under 1-ulp perturbations)."""
-    basis = okl.Basis(g["piercepoints"])
+    chaotic there: its own output changes under 1-ulp perturbations).  ``g``
+    holds ``piercepoints``, ``ref_ant`` (-1: none) and the final ``orders``
+    [T, F, A] and ``w_out`` [T, F, A, D] of a fit on the basis of ``r_0``
+    and ``beta``."""
+    basis = okl.Basis(g["piercepoints"], r_0, beta)
     ref = int(g["ref_ant"])
-    val = g["val"] - g["val"][:, :, ref:ref + 1, :]
     bad = set()
-    T, F, A, D = val.shape
+    T, F, A, D = g["w_out"].shape
     for t in range(T):
         for f in range(F):
             for a in range(A):
@@ -65,7 +67,7 @@ def ill_conditioned_slots(g):
                 if o == 0 or a == ref or not np.any(w > 0):
                     continue
                 unfl = np.where(w > 0)[0]
-                c, pc, u = okl.calculate_svd(basis.pp[unfl], 100.0, 5.0 / 3.0)
+                c, pc, u = okl.calculate_svd(basis.pp[unfl], r_0, beta)
                 uk = u[:, :o]
                 wd = np.diag(w[unfl].astype(np.float64))
                 if np.linalg.svd(uk.T @ (wd @ u)[:, :o], compute_uv=False).min() <= 1e-3:

@@ -2,7 +2,12 @@
 GPU: the fit of all slots, timed with HIP events, repeated and interleaved;
 outputs (coefficients, residuals, weights, orders) compared bit for bit.
 
-    python tools/fit_ab.py [--workload config4] [--reps 5] [--time-scale 1.0]
+    python tools/fit_ab.py [--workload config4] [--reps 5] [--weight-scale 400]
+
+--weight-scale multiplies the weights: with the workloads' weights of 1 the
+reduced chi^2 is ~ 0.003 and the order walk of adjust_order re-fits no slot;
+x 400 (1 / sigma^2 of the 0.05 rad noise) makes it re-fit about half of
+them, up to three times per pass.  The line reports how many slots moved.
 """
 import argparse
 import os
@@ -27,6 +32,8 @@ ap.add_argument("--reps", type=int, default=5)
 ap.add_argument("--times", type=int, default=0, help="time slots (0: the workload's)")
 ap.add_argument("--weights", default="01", help="01: the workload's 0/1 weights; "
                 "random: uniform(0.5, 1) weights (the general layout)")
+ap.add_argument("--weight-scale", type=float, default=1.0,
+                help="multiply the weights (400: the order walk re-fits)")
 args = ap.parse_args()
 
 A, T, F, D, N, cell = WORKLOADS[args.workload]
@@ -37,6 +44,8 @@ if args.weights == "random":
     rng = np.random.default_rng(7)
     w = sol.weight
     sol.weight[...] = np.where(w > 0, rng.uniform(0.5, 1.0, w.shape), 0).astype(w.dtype)
+if args.weight_scale != 1.0:
+    sol.weight[...] = sol.weight * np.float32(args.weight_scale)
 setup = setup_shard(sol, 0, A, FIELD_RA_DEG, FIELD_DEC_DEG, FIELD_WIDTH_DEG, cell,
                     device="cpu")
 dev = torch.device("cuda", 0)
@@ -78,7 +87,11 @@ for rep in range(args.reps + 1):
 ctx.set_option(SF_OPT_FIT_LEAN, 1)
 same = all(np.array_equal(ref[0][k].view(np.uint8), ref[1][k].view(np.uint8))
            for k in ref[0])
-print(f"{args.workload} S={S} D={D} weights={args.weights}: general "
+n_unfl = (ref[1]["w_out"] > 0).sum(axis=-1)
+start = np.minimum(np.asarray(setup["st_order"])[None, None, :], n_unfl - 1)
+moved = int(((ref[1]["order_out"] != start) & (ref[1]["order_out"] > 0)).sum())
+print(f"{args.workload} S={S} D={D} weights={args.weights} x {args.weight_scale:g} "
+      f"({moved} slots left their starting order): general "
       f"{np.median(ms[0]):.2f} ms, lean {np.median(ms[1]):.2f} ms "
       f"(x{np.median(ms[0]) / np.median(ms[1]):.2f}); outputs bit-identical: {same}",
       flush=True)
