@@ -1,30 +1,14 @@
 // kl_eval_launch.h -- host side of the D <= 60 evaluation kernels of
 // kl_eval_impl.h: one description of a call (EvalCall), one launch plan per
 // kernel family (EvalPlan, the plan_* functions: the only home of the measured
-// tuning constants), one split loop (eval_split) and one run-time-bool ->
+// tuning constants) and one split loop (eval_split); the run-time-bool ->
 // template-argument dispatch (with_bools, also used by the wide and value
-// launchers).  No kernel lives here.
+// launchers) is sf_dispatch.h's.  No kernel lives here.
 #pragma once
 #include "kl_eval_impl.h"
+#include "sf_dispatch.h"
 
 namespace sf {
-
-// f(std::bool_constant<b>{}...) for run-time bools b...: the callable reads
-// them as template arguments (decltype(B)::value).  Every combination of the
-// bools instantiates f's body, so f guards the kernel variants that do not
-// exist with `if constexpr` -- a kernel named in a discarded branch is never
-// instantiated.
-template <bool... Bs, class F>
-void with_bools(F&& f) {
-  f(std::bool_constant<Bs>{}...);
-}
-template <bool... Bs, class F, class... Rest>
-void with_bools(F&& f, bool b, Rest... rest) {
-  if (b)
-    with_bools<Bs..., true>(f, rest...);
-  else
-    with_bools<Bs..., false>(f, rest...);
-}
 
 // One evaluation call as sf_kl_eval* hands it to launch_eval
 struct EvalCall {

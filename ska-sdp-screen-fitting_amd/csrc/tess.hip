@@ -8,15 +8,25 @@
 // with g = identity or the separable Gaussian (axis y then axis x, float32
 // between the passes, 'reflect' borders, scipy's symmetric-kernel summation
 // order in float64).  sf_tess_fill runs a per-slot value-table pass and then
-// kl_tess_gather_kernel (no smoothing) or kl_tess_smooth_kernel (radius <=
-// kMaxR), both below; kl_tess_kernel, the round-1 fused kernel (one
-// workgroup = a 16 x 16 output tile and a chunk of slots, label tile + halo
-// in LDS), stays for cross-checks (SF_OPT_TESS_TILE).  In every variant the
-// only large HBM traffic is the 16 B / pixel / slot output write.
+// kl_tess_gather_kernel (no smoothing), kl_tess_smooth_kernel or
+// kl_tess_box_kernel (radius <= kMaxR), all below; kl_tess_kernel, the round-1
+// fused kernel (one workgroup = a 16 x 16 output tile and a chunk of slots,
+// label tile + halo in LDS), stays for cross-checks (SF_OPT_TESS_TILE).  In
+// every variant the only large HBM traffic is the 16 B / pixel / slot output
+// write.
+//
+// Host side, after the kernels: compiled_radius (which <radius, planes, table
+// capacity> variants exist), plan_tess (kernel kind, slot chunk, work items,
+// LDS: the home of the auto rules and option defaults) and launch_fill.  The
+// tap sums, halo-label staging and row stores are spelled out per kernel on
+// purpose: shared helpers changed registers, spills or LDS
+// (profiles/tess_launch_isa.txt).
 #include <hip/hip_runtime.h>
 
 #include <cmath>
+#include <type_traits>
 
+#include "sf_dispatch.h"
 #include "sf_internal.h"
 
 namespace sf {
@@ -39,6 +49,33 @@ __device__ __forceinline__ int reflect_idx(int i, int n) {
 // the occupancy, those kernels always had -- and 129 up to SF_MAX_EVAL_DIR.
 constexpr int kTabCap = 65;
 constexpr int kTabCapWide = SF_MAX_EVAL_DIR + 1;
+
+typedef float tess_v4f __attribute__((ext_vector_type(4)));
+
+// What every variant does to a finished value of plane p: NaN -> 1 (real
+// planes) / 0 (imaginary) under the scrub, then the FITS byte order
+__device__ __forceinline__ float scrub_swap(float x, int p, bool scrub, bool be) {
+  if (scrub && isnan(x)) x = (p & 1) ? 0.0f : 1.0f;
+  if (be) x = __uint_as_float(__builtin_bswap32(__float_as_uint(x)));
+  return x;
+}
+
+// The NP smoothed planes of a pixel (NP = 2: planes 2 / 3 repeat planes 0 / 1
+// -- no YY amplitude, A_yy = A_xx -- so only two are smoothed and each is
+// stored twice): fp64 sums, float32 between the passes like scipy's
+// intermediate image
+template <int NP>
+using tess_acc_t = double __attribute__((ext_vector_type(NP)));
+template <int NP>
+using tess_yf_t = float __attribute__((ext_vector_type(NP)));
+
+template <int NP, class V>
+__device__ __forceinline__ tess_acc_t<NP> widen(const V& v) {
+  tess_acc_t<NP> r;
+#pragma unroll
+  for (int p = 0; p < NP; ++p) r[p] = (double)v[p];
+  return r;
+}
 
 template <int TC>
 __global__ __launch_bounds__(256) void kl_tess_kernel(
@@ -123,13 +160,8 @@ __global__ __launch_bounds__(256) void kl_tess_kernel(
       // a label outside 1..D (never made by the template) reads no table
       // entry: its pixels are NaN (1 / 0 under the scrub), see sf_tess_fill
 #pragma unroll
-      for (int p = 0; p < 4; ++p) {
-        float x = v[p];
-        if (scrub && isnan(x)) x = (p & 1) ? 0.0f : 1.0f;
-        if (flags & SF_EVAL_BIG_ENDIAN)
-          x = __uint_as_float(__builtin_bswap32(__float_as_uint(x)));
-        o[p * P] = x;
-      }
+      for (int p = 0; p < 4; ++p)
+        o[p * P] = scrub_swap(v[p], p, scrub, flags & SF_EVAL_BIG_ENDIAN);
     }
   }
 }
@@ -156,8 +188,6 @@ constexpr int kGatherRun = 1024;       // pixels per workgroup (4 KiB per plane)
 constexpr int kGatherWavesAuto = 16;   // waves per workgroup (SF_OPT_TESS_WAVES)
 constexpr int kGatherSlotsAuto = 16;   // slots per work item (SF_OPT_TESS_SLOTS)
 
-typedef float tess_v4f __attribute__((ext_vector_type(4)));
-
 __global__ __launch_bounds__(256) void kl_tess_table_kernel(
     const double* __restrict__ phase, const double* __restrict__ amp_xx,
     const double* __restrict__ amp_yy, int D, int64_t S,
@@ -182,11 +212,8 @@ __global__ __launch_bounds__(256) void kl_tess_table_kernel(
     v[0] = v[1] = v[2] = v[3] = __builtin_nanf("");
   }
 #pragma unroll
-  for (int p = 0; p < 4; ++p) {
-    if ((flags & SF_EVAL_NAN_SCRUB) && isnan(v[p])) v[p] = (p & 1) ? 0.0f : 1.0f;
-    if (flags & SF_EVAL_BIG_ENDIAN)
-      v[p] = __uint_as_float(__builtin_bswap32(__float_as_uint(v[p])));
-  }
+  for (int p = 0; p < 4; ++p)
+    v[p] = scrub_swap(v[p], p, flags & SF_EVAL_NAN_SCRUB, flags & SF_EVAL_BIG_ENDIAN);
   tab[e] = tess_v4f{v[0], v[1], v[2], v[3]};
 }
 
@@ -281,16 +308,8 @@ __global__ __launch_bounds__(256) void kl_tess_smooth_kernel(
     const double* __restrict__ gw, int R_arg, int64_t n_tiles, int64_t n_sc,
     unsigned flags) {
 #pragma clang fp contract(off)
-  // NP = 2: planes 2 / 3 repeat planes 0 / 1 (no YY amplitude: A_yy = A_xx),
-  // so only two planes are smoothed and each is stored twice
-  typedef double vacc_t __attribute__((ext_vector_type(NP)));
-  typedef float vyf_t __attribute__((ext_vector_type(NP)));
-  auto widen = [](const auto& v) {
-    vacc_t r;
-#pragma unroll
-    for (int p = 0; p < NP; ++p) r[p] = (double)v[p];
-    return r;
-  };
+  typedef tess_acc_t<NP> vacc_t;
+  typedef tess_yf_t<NP> vyf_t;
   constexpr int kR = RT > 0 ? RT : kMaxR;  // LDS sizing
   constexpr int kSmTH = smooth_rows(RT);
   const int R = RT > 0 ? RT : R_arg;
@@ -326,7 +345,7 @@ __global__ __launch_bounds__(256) void kl_tess_smooth_kernel(
       lab[e] = (unsigned char)((lb >= 0 && lb < D) ? lb : D);
     }
     for (int e = threadIdx.x; e < DT; e += blockDim.x) {
-      tbl[0][e] = widen(tab[s0 * DT + e]);
+      tbl[0][e] = widen<NP>(tab[s0 * DT + e]);
     }
     for (int k = 0; k < ns; ++k) {
       __syncthreads();  // tbl[k & 1] (and, at k = 0, lab) complete; ybuf free
@@ -376,7 +395,7 @@ __global__ __launch_bounds__(256) void kl_tess_smooth_kernel(
       // finished the y pass of slot k - 1 before the barrier above)
       if (k + 1 < ns)
         for (int e = threadIdx.x; e < DT; e += blockDim.x) {
-          tbl[(k + 1) & 1][e] = widen(tab[(s0 + k + 1) * DT + e]);
+          tbl[(k + 1) & 1][e] = widen<NP>(tab[(s0 + k + 1) * DT + e]);
         }
       __syncthreads();
       // x pass: wave w takes rows w, w + 4, ...; 4 pixels per lane
@@ -391,7 +410,7 @@ __global__ __launch_bounds__(256) void kl_tess_smooth_kernel(
       if constexpr (RT > 0) {
         const vyf_t* base = ybuf + rr * W2 + 4 * l;
 #pragma unroll
-        for (int h = 0; h < XW; ++h) xwin[h] = widen(base[h]);
+        for (int h = 0; h < XW; ++h) xwin[h] = widen<NP>(base[h]);
       }
 #pragma unroll
       for (int i = 0; i < 4; ++i) {
@@ -403,19 +422,14 @@ __global__ __launch_bounds__(256) void kl_tess_smooth_kernel(
             acc += (xwin[RT + i - j] + xwin[RT + i + j]) * w[RT - j];
         } else {
           const vyf_t* row = ybuf + rr * W2 + R + 4 * l + i;
-          acc = widen(row[0]) * w[R];
+          acc = widen<NP>(row[0]) * w[R];
 #pragma unroll kTapUnroll
           for (int j = R; j >= 1; --j) {
-            acc += (widen(row[-j]) + widen(row[j])) * w[R - j];
+            acc += (widen<NP>(row[-j]) + widen<NP>(row[j])) * w[R - j];
           }
         }
 #pragma unroll
-        for (int p = 0; p < 4; ++p) {
-          float x = (float)acc[p % NP];
-          if (scrub && isnan(x)) x = (p & 1) ? 0.0f : 1.0f;
-          if (be) x = __uint_as_float(__builtin_bswap32(__float_as_uint(x)));
-          v[i][p] = x;
-        }
+        for (int p = 0; p < 4; ++p) v[i][p] = scrub_swap((float)acc[p % NP], p, scrub, be);
       }
       const int64_t so = (s0 + k + ring_base) % ring;
       float* o = out + so * 4 * P + (int64_t)gy * nx + gx0;
@@ -468,14 +482,8 @@ __global__ __launch_bounds__(256) void kl_tess_box_kernel(
     const double* __restrict__ gw, int R_arg, int64_t n_tiles, int64_t n_sc,
     unsigned flags) {
 #pragma clang fp contract(off)
-  typedef double vacc_t __attribute__((ext_vector_type(NP)));
-  typedef float vyf_t __attribute__((ext_vector_type(NP)));
-  auto widen = [](const auto& v) {
-    vacc_t r;
-#pragma unroll
-    for (int p = 0; p < NP; ++p) r[p] = (double)v[p];
-    return r;
-  };
+  typedef tess_acc_t<NP> vacc_t;
+  typedef tess_yf_t<NP> vyf_t;
   constexpr int kR = RT > 0 ? RT : kBoxMaxR;  // LDS sizing
   constexpr int kW2 = kSmTW + 2 * kR;
   constexpr unsigned char kMixed = 0xFF;       // D <= 128 < 0xFF
@@ -508,7 +516,7 @@ __global__ __launch_bounds__(256) void kl_tess_box_kernel(
   // value and its uniform-box final value (scipy's order on equal inputs)
   auto entry_tables = [&](int64_t s, int b) {
     for (int e = tid; e < DT; e += blockDim.x) {
-      const vacc_t t = widen(tab[s * DT + e]);
+      const vacc_t t = widen<NP>(tab[s * DT + e]);
       tbl[b][e] = t;
       vacc_t acc = t * w[R];
       for (int j = R; j >= 1; --j) acc += (t + t) * w[R - j];
@@ -516,17 +524,12 @@ __global__ __launch_bounds__(256) void kl_tess_box_kernel(
 #pragma unroll
       for (int p = 0; p < NP; ++p) y[p] = (float)acc[p];
       yu[b][e] = y;
-      const vacc_t yd = widen(y);
+      const vacc_t yd = widen<NP>(y);
       acc = yd * w[R];
       for (int j = R; j >= 1; --j) acc += (yd + yd) * w[R - j];
       tess_v4f v;
 #pragma unroll
-      for (int p = 0; p < 4; ++p) {
-        float x = (float)acc[p % NP];
-        if (scrub && isnan(x)) x = (p & 1) ? 0.0f : 1.0f;
-        if (be) x = __uint_as_float(__builtin_bswap32(__float_as_uint(x)));
-        v[p] = x;
-      }
+      for (int p = 0; p < 4; ++p) v[p] = scrub_swap((float)acc[p % NP], p, scrub, be);
       xu[b][e] = v;
     }
   };
@@ -594,19 +597,14 @@ __global__ __launch_bounds__(256) void kl_tess_box_kernel(
         const int c0 = r * W2 + x + R;
         auto ycol = [&](int c) -> vacc_t {
           const unsigned char L = vlab[c];
-          return widen(L != kMixed ? yu[b][L] : ybuf[c]);
+          return widen<NP>(L != kMixed ? yu[b][L] : ybuf[c]);
         };
         vacc_t acc = ycol(c0) * w[R];
 #pragma unroll kTapUnroll
         for (int j = R; j >= 1; --j) acc += (ycol(c0 - j) + ycol(c0 + j)) * w[R - j];
         tess_v4f v;
 #pragma unroll
-        for (int p = 0; p < 4; ++p) {
-          float xv = (float)acc[p % NP];
-          if (scrub && isnan(xv)) xv = (p & 1) ? 0.0f : 1.0f;
-          if (be) xv = __uint_as_float(__builtin_bswap32(__float_as_uint(xv)));
-          v[p] = xv;
-        }
+        for (int p = 0; p < 4; ++p) v[p] = scrub_swap((float)acc[p % NP], p, scrub, be);
         xout[e] = v;
       }
       __syncthreads();
@@ -671,6 +669,8 @@ __global__ __launch_bounds__(256) void smooth_pass_kernel(
   };
   double acc = at(0) * gw[R];
   for (int j = R; j >= 1; --j) acc += (at(-j) + at(j)) * gw[R - j];
+  // scrub_swap written out: through the helper this kernel compiles to other
+  // code (profiles/tess_launch_isa.txt)
   float v = (float)acc;
   if (flags & SF_EVAL_NAN_SCRUB) {
     // plane = image index mod 4 (cube [.][4][ny][nx]): 1.0 real, 0.0 imag
@@ -679,6 +679,32 @@ __global__ __launch_bounds__(256) void smooth_pass_kernel(
   if (flags & SF_EVAL_BIG_ENDIAN)
     v = __uint_as_float(__builtin_bswap32(__float_as_uint(v)));
   out[e] = v;
+}
+
+// ---------------------------------------------------------------- host ----
+
+// A grow-only scratch buffer of the context (the value table, the pass
+// buffer): at least `need` bytes.  The old buffer is freed before the new one
+// is allocated, so the two never coexist; a failed allocation leaves none.
+template <class T>
+static int scratch_reserve(T** buf, size_t* cap, size_t need, const char* what) {
+  if (*cap >= need) return SF_OK;
+  if (*buf) (void)hipFree(*buf);
+  *buf = nullptr;
+  *cap = 0;
+  if (hipMalloc(reinterpret_cast<void**>(buf), need) != hipSuccess) {
+    set_error(what);
+    return SF_ENOMEM;
+  }
+  *cap = need;
+  return SF_OK;
+}
+
+// Workgroups of `threads` for n_items work items: one each up to the dispatch
+// limit (2^32 work-items, kept at 2^31); past it the workgroups walk the rest
+static unsigned walk_grid(int64_t n_items, int threads) {
+  const int64_t cap = ((int64_t)1 << 31) / threads;
+  return (unsigned)(n_items < cap ? n_items : cap);
 }
 
 int launch_smooth(sf_ctx* ctx, float* cube, int nx, int ny, int64_t n_img,
@@ -690,17 +716,8 @@ int launch_smooth(sf_ctx* ctx, float* cube, int nx, int ny, int64_t n_img,
   if (chunk < 4) chunk = 4;
   chunk &= ~(int64_t)3;  // whole [4][ny][nx] slot cubes (plane = img % 4)
   if (chunk > n_img) chunk = n_img;
-  const size_t need = (size_t)(chunk * P) * sizeof(float);
-  if (ctx->smooth_cap < need) {
-    if (ctx->d_smooth) (void)hipFree(ctx->d_smooth);
-    ctx->d_smooth = nullptr;
-    ctx->smooth_cap = 0;
-    if (hipMalloc(reinterpret_cast<void**>(&ctx->d_smooth), need) != hipSuccess) {
-      set_error("sf_smooth: hipMalloc of the pass buffer failed");
-      return SF_ENOMEM;
-    }
-    ctx->smooth_cap = need;
-  }
+  SF_TRY_RC(scratch_reserve(&ctx->d_smooth, &ctx->smooth_cap, (size_t)(chunk * P) * sizeof(float),
+                            "sf_smooth: hipMalloc of the pass buffer failed"));
   for (int64_t i0 = 0; i0 < n_img; i0 += chunk) {
     const int64_t ni = (n_img - i0 < chunk) ? n_img - i0 : chunk;
     const int64_t n = ni * P;
@@ -717,205 +734,157 @@ int launch_smooth(sf_ctx* ctx, float* cube, int nx, int ny, int64_t n_img,
   return SF_OK;
 }
 
-// The value table of at most `per` slots (<= 256 MiB of scratch, a multiple
-// of `chunk`) in the context's scratch buffer.
-static int tess_table_alloc(sf_ctx* ctx, int64_t S, int64_t DT, int chunk,
-                            int64_t* per_out) {
-  int64_t per = (((int64_t)256 << 20) / (DT * 16)) / chunk * chunk;
-  if (per < chunk) per = chunk;
-  if (per > S) per = S;
-  const size_t need = (size_t)(per * DT) * 16;
-  if (ctx->tess_tab_cap < need) {
-    if (ctx->d_tess_tab) (void)hipFree(ctx->d_tess_tab);
-    ctx->d_tess_tab = nullptr;
-    ctx->tess_tab_cap = 0;
-    if (hipMalloc(reinterpret_cast<void**>(&ctx->d_tess_tab), need) != hipSuccess) {
-      set_error("sf_tess_fill: hipMalloc of the value table failed");
-      return SF_ENOMEM;
-    }
-    ctx->tess_tab_cap = need;
-  }
-  *per_out = per;
-  return SF_OK;
+enum TessKind { kTessGather, kTessSmooth, kTessBox };
+
+constexpr int tab_cap(bool wide) { return wide ? kTabCapWide : kTabCap; }
+
+// The compiled radii: radius R runs in the instantiation <RT, NP, TC> of its
+// kernel with RT = compiled_radius(...) -- R where that variant is compiled,
+// else 0, the run-time radius (same bits, LDS sized for kMaxR).  The launch
+// below names no other <RT, NP, TC>, so this is all that is instantiated.
+//  * interior lookups, and the wide tile with 129-entry tables: sigma <= 2 px
+//    (R <= 8);
+//  * wide tile, 65-entry tables: R <= 11, and up to kMaxR with two planes
+//    (with four, the unrolled tap windows of R >= 12 would spill).
+constexpr int compiled_radius(TessKind kind, int NP, int TC, int R) {
+  if (R < 1 || R > kMaxR) return 0;
+  if (kind == kTessBox || TC > kTabCap) return R <= 8 ? R : 0;
+  return R <= 11 || NP == 2 ? R : 0;
 }
 
-int launch_tess(sf_ctx* ctx, const int32_t* labels, int nx, int ny,
-                const double* phase, const double* amp_xx,
-                const double* amp_yy, int D, int64_t S, float* out,
-                int64_t ring, const double* d_w, int R, unsigned flags) {
-  const int64_t P = (int64_t)nx * ny;
-  const int64_t DT = D + 1;
+// One fill as sf_tess_fill hands it to launch_tess
+struct TessCall {
+  sf_ctx* ctx;
+  const int32_t* labels;
+  const double *phase, *amp_xx, *amp_yy;  // [S][D]; amplitudes or null
+  const double* d_w;                      // Gaussian weights of radius R
+  float* out;
+  int nx, ny, D, R;  // R = 0: unsmoothed
+  int64_t S, ring;
+  unsigned flags;
+};
+
+// How a fill runs: the kernel that follows the value-table kernel and its
+// work items (pixel item, slot chunk)
+struct TessPlan {
+  TessKind kind;
+  int chunk;           // slots per work item
+  int threads;         // per workgroup
+  int64_t n_items;     // work items along pixels: tiles (n_tiles) or runs (n_pb)
+  size_t lds;          // dynamic LDS: the gather's table slice
+  bool vec4;           // gather: float4 stores
+  unsigned tab_flags;  // scrub / swap applied to the table entries
+};
+
+static TessPlan plan_tess(const TessCall& c) {
+  const sf_ctx* ctx = c.ctx;
+  const int64_t DT = c.D + 1;
+  const int64_t tiles_x = (c.nx + kSmTW - 1) / kSmTW;
+  TessPlan p{};
+  p.threads = 256;
+  if (c.R == 0) {
+    // unsmoothed, the table entries are the pixels: scrub / swap them there
+    p.kind = kTessGather;
+    p.tab_flags = c.flags;
+    // the item's table slice in LDS: at most 64 KiB (63 slots at D = 64, 31
+    // at D = 128; D <= SF_MAX_EVAL_DIR keeps the clamped chunk >= 1)
+    p.chunk = ctx->tess_slots > 0 ? ctx->tess_slots : kGatherSlotsAuto;
+    if (p.chunk * DT * 16 > 65536) p.chunk = (int)(65536 / (DT * 16));
+    p.lds = (size_t)p.chunk * DT * 16;
+    const int64_t P = (int64_t)c.nx * c.ny;
+    p.vec4 = (P % 4 == 0) && ((reinterpret_cast<uintptr_t>(c.out) & 15) == 0);
+    // SF_OPT_TESS_WAVES: 4, 8 or (auto, and anything else) kGatherWavesAuto;
+    // the scalar-store kernel exists at 4 waves only
+    const int nw = ctx->tess_waves;
+    p.threads = 64 * (!p.vec4 || nw == 4 ? 4 : nw == 8 ? 8 : kGatherWavesAuto);
+    p.n_items = (P + kGatherRun - 1) / kGatherRun;
+    return p;
+  }
   // smoothing: the interior-lookup kernel or the wide-tile kernel
   // (SF_OPT_TESS_BOX; auto: interior lookups for four planes at R <= 5, where
   // the wide-tile kernel is fp64-VALU-bound -- sigma 0.25 / 0.5 / 0.75 / 1 /
   // 1.25 px: 0.66 / 0.51 / 0.42 / 0.35 / 0.31 -> 0.73 / 0.73 / 0.59 / 0.44 /
   // 0.37 of 8 TB/s; with two planes, or at R = 8, the wide-tile kernel's
   // sliding windows win: profiles/round3p_tess_box_sweep.txt)
-  const bool box = R > 0 && R <= kBoxMaxR &&
-                   (ctx->tess_box == 1 || (ctx->tess_box < 0 && amp_yy && R <= 5));
-  // D > 64: the kernels with the larger LDS tables
-  const bool wide = D + 1 > kTabCap;
-  int chunk = box ? kBoxSlots : kSmSlots;
-  if (R == 0) {
-    // the item's table slice in LDS: at most 64 KiB (63 slots at D = 64, 31
-    // at D = 128; D <= SF_MAX_EVAL_DIR keeps the clamped chunk >= 1)
-    chunk = ctx->tess_slots > 0 ? ctx->tess_slots : kGatherSlotsAuto;
-    if (chunk * DT * 16 > 65536) chunk = (int)(65536 / (DT * 16));
+  const bool box = c.R <= kBoxMaxR &&
+                   (ctx->tess_box == 1 || (ctx->tess_box < 0 && c.amp_yy && c.R <= 5));
+  p.kind = box ? kTessBox : kTessSmooth;
+  p.chunk = box ? kBoxSlots : kSmSlots;
+  const int rows = box ? kBoxTH : smooth_rows(c.R);  // the kernel's tile rows
+  p.n_items = tiles_x * ((c.ny + rows - 1) / rows);
+  return p;
+}
+
+// The planned kernel over the Sb slots from slot b of the call (table: `tab`)
+static void launch_fill(const TessCall& c, const TessPlan& p, const tess_v4f* tab, int64_t b,
+                        int64_t Sb) {
+  const int64_t n_sc = (Sb + p.chunk - 1) / p.chunk;
+  const dim3 grid(walk_grid(p.n_items * n_sc, p.threads)), block(p.threads);
+  const int64_t ring_base = b % c.ring;
+  hipStream_t stream = c.ctx->stream;
+  if (p.kind == kTessGather) {
+    auto gather = [&](auto NW, auto V) {
+      hipLaunchKernelGGL((kl_tess_gather_kernel<decltype(NW)::value, decltype(V)::value>), grid,
+                         block, p.lds, stream, c.labels, (int64_t)c.nx * c.ny, tab, c.D, Sb,
+                         c.out, c.ring, ring_base, p.n_items, n_sc, p.chunk);
+    };
+    if (!p.vec4)
+      gather(std::integral_constant<int, 4>{}, std::false_type{});
+    else if (p.threads == 64 * 4)
+      gather(std::integral_constant<int, 4>{}, std::true_type{});
+    else if (p.threads == 64 * 8)
+      gather(std::integral_constant<int, 8>{}, std::true_type{});
+    else
+      gather(std::integral_constant<int, kGatherWavesAuto>{}, std::true_type{});
+    return;
   }
-  int64_t per = 0;
-  const int rc = tess_table_alloc(ctx, S, DT, chunk, &per);
-  if (rc != SF_OK) return rc;
+  with_bools(
+      [&](auto BOX, auto YY, auto WIDE) {
+        constexpr TessKind kind = decltype(BOX)::value ? kTessBox : kTessSmooth;
+        constexpr int NP = decltype(YY)::value ? 4 : 2;
+        constexpr int TC = tab_cap(decltype(WIDE)::value);
+        with_radius<kMaxR>(c.R, [&](auto RC) {
+          constexpr int r = decltype(RC)::value;
+          constexpr int RT = compiled_radius(kind, NP, TC, r);
+          // (the plan's tile rows, smooth_rows(R), are the instantiation's)
+          static_assert(RT == r || (RT == 0 && smooth_rows(0) == smooth_rows(r)),
+                        "a radius runs compiled in, or at run time on the same tile");
+          auto launch = [&](auto kernel) {
+            hipLaunchKernelGGL(kernel, grid, block, 0, stream, c.labels, c.nx, c.ny, tab, c.D, Sb,
+                               c.out, c.ring, ring_base, c.d_w, c.R, p.n_items, n_sc, c.flags);
+          };
+          if constexpr (kind == kTessBox)
+            launch(kl_tess_box_kernel<RT, NP, TC>);
+          else
+            launch(kl_tess_smooth_kernel<RT, NP, TC>);
+        });
+      },
+      p.kind == kTessBox, c.amp_yy != nullptr, c.D + 1 > kTabCap);
+}
+
+int launch_tess(sf_ctx* ctx, const int32_t* labels, int nx, int ny,
+                const double* phase, const double* amp_xx,
+                const double* amp_yy, int D, int64_t S, float* out,
+                int64_t ring, const double* d_w, int R, unsigned flags) {
+  const TessCall c{ctx, labels, phase, amp_xx, amp_yy, d_w, out, nx, ny, D, R, S, ring, flags};
+  const TessPlan p = plan_tess(c);
+  // the value table of at most `per` slots (<= 256 MiB of scratch, a multiple
+  // of the chunk) in the context's scratch buffer
+  const int64_t DT = D + 1;
+  int64_t per = (((int64_t)256 << 20) / (DT * 16)) / p.chunk * p.chunk;
+  if (per < p.chunk) per = p.chunk;
+  if (per > S) per = S;
+  SF_TRY_RC(scratch_reserve(&ctx->d_tess_tab, &ctx->tess_tab_cap, (size_t)(per * DT) * 16,
+                            "sf_tess_fill: hipMalloc of the value table failed"));
   tess_v4f* tab = reinterpret_cast<tess_v4f*>(ctx->d_tess_tab);
-  // unsmoothed, the table entries are the pixels: scrub / swap them there
-  const unsigned tab_flags = R == 0 ? flags : 0u;
   for (int64_t b = 0; b < S; b += per) {
     const int64_t Sb = S - b < per ? S - b : per;
-    const int64_t n_tab = Sb * DT;
-    hipLaunchKernelGGL(kl_tess_table_kernel, dim3((unsigned)((n_tab + 255) / 256)),
+    hipLaunchKernelGGL(kl_tess_table_kernel, dim3((unsigned)((Sb * DT + 255) / 256)),
                        dim3(256), 0, ctx->stream, phase + b * D,
                        amp_xx ? amp_xx + b * D : nullptr,
-                       amp_yy ? amp_yy + b * D : nullptr, D, Sb, tab, tab_flags);
+                       amp_yy ? amp_yy + b * D : nullptr, D, Sb, tab, p.tab_flags);
     SF_HIP(hipGetLastError());
-    const int64_t n_sc = (Sb + chunk - 1) / chunk;
-    if (box) {
-      const int64_t n_tiles = (int64_t)((nx + kSmTW - 1) / kSmTW) * ((ny + kBoxTH - 1) / kBoxTH);
-      int64_t grid = n_tiles * n_sc;
-      const int64_t cap = ((int64_t)1 << 31) / 256;
-      if (grid > cap) grid = cap;  // workgroups walk the remaining items
-#define SF_BOX_T(RT, NP, TC)                                                        \
-  hipLaunchKernelGGL((kl_tess_box_kernel<RT, NP, TC>), dim3((unsigned)grid),        \
-                     dim3(256), 0, ctx->stream, labels, nx, ny, tab, D, Sb, out,    \
-                     ring, b % ring, d_w, R, n_tiles, n_sc, flags)
-#define SF_BOX(RT)                                                                  \
-  do {                                                                              \
-    if (wide) {                                                                     \
-      if (amp_yy) SF_BOX_T(RT, 4, kTabCapWide);                                     \
-      else SF_BOX_T(RT, 2, kTabCapWide);                                            \
-    } else {                                                                        \
-      if (amp_yy) SF_BOX_T(RT, 4, kTabCap);                                         \
-      else SF_BOX_T(RT, 2, kTabCap);                                                \
-    }                                                                               \
-  } while (0)
-      // compiled radii: sigma up to 2 px (R <= 8); wider ones run the
-      // run-time radius variant
-      switch (R) {
-        case 1: SF_BOX(1); break;
-        case 2: SF_BOX(2); break;
-        case 3: SF_BOX(3); break;
-        case 4: SF_BOX(4); break;
-        case 5: SF_BOX(5); break;
-        case 6: SF_BOX(6); break;
-        case 7: SF_BOX(7); break;
-        case 8: SF_BOX(8); break;
-        default: SF_BOX(0);
-      }
-#undef SF_BOX
-#undef SF_BOX_T
-      SF_HIP(hipGetLastError());
-      continue;
-    }
-    if (R > 0) {
-      const int rows = smooth_rows(R);  // the kernel's kSmTH (8 for every R > 2)
-      const int64_t n_tiles = (int64_t)((nx + kSmTW - 1) / kSmTW) * ((ny + rows - 1) / rows);
-      int64_t grid = n_tiles * n_sc;
-      const int64_t cap = ((int64_t)1 << 31) / 256;
-      if (grid > cap) grid = cap;  // workgroups walk the remaining items
-#define SF_SMOOTH(RT)                                                               \
-  do {                                                                              \
-    if (amp_yy)                                                                     \
-      hipLaunchKernelGGL((kl_tess_smooth_kernel<RT, 4>), dim3((unsigned)grid),      \
-                         dim3(256), 0, ctx->stream, labels, nx, ny, tab, D, Sb, out, \
-                         ring, b % ring, d_w, R, n_tiles, n_sc, flags);             \
-    else                                                                            \
-      hipLaunchKernelGGL((kl_tess_smooth_kernel<RT, 2>), dim3((unsigned)grid),      \
-                         dim3(256), 0, ctx->stream, labels, nx, ny, tab, D, Sb, out, \
-                         ring, b % ring, d_w, R, n_tiles, n_sc, flags);             \
-  } while (0)
-#define SF_SMOOTH2(RT)                                                              \
-  hipLaunchKernelGGL((kl_tess_smooth_kernel<RT, 2>), dim3((unsigned)grid), dim3(256), \
-                     0, ctx->stream, labels, nx, ny, tab, D, Sb, out, ring, b % ring,  \
-                     d_w, R, n_tiles, n_sc, flags)
-#define SF_SMOOTH_W(RT)                                                             \
-  do {                                                                              \
-    if (amp_yy)                                                                     \
-      hipLaunchKernelGGL((kl_tess_smooth_kernel<RT, 4, kTabCapWide>),               \
-                         dim3((unsigned)grid), dim3(256), 0, ctx->stream, labels,   \
-                         nx, ny, tab, D, Sb, out, ring, b % ring, d_w, R, n_tiles,  \
-                         n_sc, flags);                                              \
-    else                                                                            \
-      hipLaunchKernelGGL((kl_tess_smooth_kernel<RT, 2, kTabCapWide>),               \
-                         dim3((unsigned)grid), dim3(256), 0, ctx->stream, labels,   \
-                         nx, ny, tab, D, Sb, out, ring, b % ring, d_w, R, n_tiles,  \
-                         n_sc, flags);                                              \
-  } while (0)
-      // D > 64: the radii of sigma <= 2 px compiled, wider ones at run time
-      // (same bits)
-      if (wide) switch (R) {
-        case 1: SF_SMOOTH_W(1); break;
-        case 2: SF_SMOOTH_W(2); break;
-        case 3: SF_SMOOTH_W(3); break;
-        case 4: SF_SMOOTH_W(4); break;
-        case 5: SF_SMOOTH_W(5); break;
-        case 6: SF_SMOOTH_W(6); break;
-        case 7: SF_SMOOTH_W(7); break;
-        case 8: SF_SMOOTH_W(8); break;
-        default: SF_SMOOTH_W(0);
-      } else
-      switch (R) {
-        case 1: SF_SMOOTH(1); break;
-        case 2: SF_SMOOTH(2); break;
-        case 3: SF_SMOOTH(3); break;
-        case 4: SF_SMOOTH(4); break;
-        case 5: SF_SMOOTH(5); break;
-        case 6: SF_SMOOTH(6); break;
-        case 7: SF_SMOOTH(7); break;
-        case 8: SF_SMOOTH(8); break;
-        // R = 9..11 compiled for both plane counts, 12..24 for two planes
-        // only (four would spill); four-plane calls there take the run-time
-        // radius kernel
-        case 9: SF_SMOOTH(9); break;
-        case 10: SF_SMOOTH(10); break;
-        case 11: SF_SMOOTH(11); break;
-        case 12: if (!amp_yy) { SF_SMOOTH2(12); break; } SF_SMOOTH(0); break;
-        case 13: if (!amp_yy) { SF_SMOOTH2(13); break; } SF_SMOOTH(0); break;
-        case 14: if (!amp_yy) { SF_SMOOTH2(14); break; } SF_SMOOTH(0); break;
-        case 15: if (!amp_yy) { SF_SMOOTH2(15); break; } SF_SMOOTH(0); break;
-        case 16: if (!amp_yy) { SF_SMOOTH2(16); break; } SF_SMOOTH(0); break;
-        case 17: if (!amp_yy) { SF_SMOOTH2(17); break; } SF_SMOOTH(0); break;
-        case 18: if (!amp_yy) { SF_SMOOTH2(18); break; } SF_SMOOTH(0); break;
-        case 19: if (!amp_yy) { SF_SMOOTH2(19); break; } SF_SMOOTH(0); break;
-        case 20: if (!amp_yy) { SF_SMOOTH2(20); break; } SF_SMOOTH(0); break;
-        case 21: if (!amp_yy) { SF_SMOOTH2(21); break; } SF_SMOOTH(0); break;
-        case 22: if (!amp_yy) { SF_SMOOTH2(22); break; } SF_SMOOTH(0); break;
-        case 23: if (!amp_yy) { SF_SMOOTH2(23); break; } SF_SMOOTH(0); break;
-        case 24: if (!amp_yy) { SF_SMOOTH2(24); break; } SF_SMOOTH(0); break;
-        default: SF_SMOOTH(0);
-      }
-#undef SF_SMOOTH
-#undef SF_SMOOTH2
-#undef SF_SMOOTH_W
-      SF_HIP(hipGetLastError());
-      continue;
-    }
-    const int64_t n_pb = (P + kGatherRun - 1) / kGatherRun;
-    const size_t lds = (size_t)chunk * DT * 16;
-    const bool vec4 = (P % 4 == 0) && ((reinterpret_cast<uintptr_t>(out) & 15) == 0);
-    int64_t grid = n_pb * n_sc;
-    const int nw = ctx->tess_waves > 0 ? ctx->tess_waves : kGatherWavesAuto;
-    const int64_t cap = ((int64_t)1 << 31) / (64 * nw);
-    if (grid > cap) grid = cap;  // workgroups walk the remaining items
-#define SF_GATHER(NW, V)                                                          \
-  hipLaunchKernelGGL((kl_tess_gather_kernel<NW, V>), dim3((unsigned)grid),       \
-                     dim3(64 * NW), lds, ctx->stream, labels, P, tab, D, Sb, out, \
-                     ring, b % ring, n_pb, n_sc, chunk)
-    if (vec4) {
-      if (nw == 4) SF_GATHER(4, true);
-      else if (nw == 8) SF_GATHER(8, true);
-      else SF_GATHER(16, true);
-    } else {
-      SF_GATHER(4, false);
-    }
-#undef SF_GATHER
+    launch_fill(c, p, tab, b, Sb);
     SF_HIP(hipGetLastError());
   }
   return SF_OK;
@@ -929,14 +898,13 @@ int launch_tess_tile(sf_ctx* ctx, const int32_t* labels, int nx, int ny,
                      int64_t ring, const double* d_w, int R, unsigned flags) {
   const int tiles = ((nx + kTT - 1) / kTT) * ((ny + kTT - 1) / kTT);
   const int64_t chunks = (S + kTessSlots - 1) / kTessSlots;
-  if (D + 1 > kTabCap)
-    hipLaunchKernelGGL(kl_tess_kernel<kTabCapWide>, dim3(tiles, (unsigned)chunks),
-                       dim3(256), 0, ctx->stream, labels, nx, ny, phase, amp_xx,
-                       amp_yy, D, S, out, ring, d_w, R, flags);
-  else
-    hipLaunchKernelGGL(kl_tess_kernel<kTabCap>, dim3(tiles, (unsigned)chunks),
-                       dim3(256), 0, ctx->stream, labels, nx, ny, phase, amp_xx,
-                       amp_yy, D, S, out, ring, d_w, R, flags);
+  with_bools(
+      [&](auto WIDE) {
+        hipLaunchKernelGGL(kl_tess_kernel<tab_cap(decltype(WIDE)::value)>,
+                           dim3(tiles, (unsigned)chunks), dim3(256), 0, ctx->stream, labels, nx,
+                           ny, phase, amp_xx, amp_yy, D, S, out, ring, d_w, R, flags);
+      },
+      D + 1 > kTabCap);
   SF_HIP(hipGetLastError());
   return SF_OK;
 }
