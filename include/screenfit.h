@@ -475,6 +475,39 @@ int sf_kl_eval_values(sf_ctx* ctx, const double* coef, int64_t S, float* out,
                       int64_t ring_slots, unsigned flags);
 
 /*
+ * Polarized phase screens (kl_eval_pol.hip): the a-term of a DIAGONAL gain
+ * whose XX and YY terms each carry their own phase, as the phase000 soltab of
+ * a diagonal-mode solve does on its pol axis.  Extends the gain screens of
+ * kl_screen.py:319-378, which take ONE phase per slot; the reference has no
+ * polarized-phase rendering.  Device coefficient arrays [S][D] float64 on the
+ * same pixel basis; with phi_p = sum_d Cpix[.][d] * phase_p[s][d] and
+ * a_p = 10^(sum_d Cpix[.][d] * amp_p[s][d]) it writes
+ *   out[(s % ring_slots)][4][ny][nx] =
+ *       (a_xx cos phi_xx, a_xx sin phi_xx, a_yy cos phi_yy, a_yy sin phi_yy)
+ * (device float32).  phase_xx and phase_yy are both required; amp_xx and
+ * amp_yy are both given or both NULL (a_p = 1); anything else is SF_EINVAL.
+ * The contractions are float64 and share the Cpix operand; the reduction in
+ * revolutions is exact (SF_EVAL_FAST_SINCOS; without the flag fp64 sincos and
+ * fp64 10^x with one cast).  With phase_yy == phase_xx the cube is bit for bit
+ * what SF_EVAL_KERNEL_WIDE gives for sf_kl_eval / sf_kl_eval_gain.  Needs
+ * sf_set_grid on the geometry of sf_set_basis, sf_set_basis_wide or
+ * sf_set_piercepoints; one kernel serves 1 <= D <= SF_MAX_EVAL_DIR.
+ * flags: SF_EVAL_NAN_SCRUB, SF_EVAL_FAST_SINCOS, SF_EVAL_NT_STORES (honoured
+ * for 16-byte-aligned output and nx * ny % 4 == 0), SF_EVAL_BIG_ENDIAN; any
+ * other bit is SF_EINVAL.  The output needs 4-byte alignment only.  NaN
+ * semantics are per polarization: a NaN coefficient of phase_yy or amp_yy in
+ * slot k gives NaN in planes 2 and 3 of slot k (1 / 0 under the scrub) and
+ * touches nothing else -- planes 0 and 1 of slot k are the bits of a clean run
+ * -- and likewise for XX.  ring_slots >= S gives every slot its own place; with
+ * a shorter ring an entry ends up holding the last slot that maps to it.  No
+ * checksums.  SF_OPT_EVAL_MAX_BLOCKS, _GROUPS, _BANDS and _XCD_MAP are
+ * honoured.  Enqueued on the context stream; does not synchronise.
+ */
+int sf_kl_eval_pol(sf_ctx* ctx, const double* phase_xx, const double* phase_yy,
+                   const double* amp_xx, const double* amp_yy, int64_t S,
+                   float* out, int64_t ring_slots, unsigned flags);
+
+/*
  * Jones cubes of TEC screens at many channels (kl_tec.hip).  The phase of a
  * TEC screen at frequency nu is rad_per_tecu * dTEC with rad_per_tecu =
  * tec_to_phase / nu, so the F channels of one (time, station) share one
@@ -564,6 +597,22 @@ int sf_tess_fill(sf_ctx* ctx, const int32_t* labels, int nx, int ny,
                  const double* phase, const double* amp_xx,
                  const double* amp_yy, int D, int64_t S, float* out,
                  int64_t ring_slots, double smooth_pix, unsigned flags);
+/*
+ * sf_tess_fill for tables with polarized phases: phase_yy [S][D] float64
+ * (device, already referenced) is the phase of the YY term, so planes 2 and 3
+ * take A_yy cos / sin of phase_yy where sf_tess_fill repeats the phase of
+ * planes 0 and 1.  Extends voronoi_screen.py:132-216, which fills one phase
+ * per direction; the reference has no polarized-phase rendering.  With
+ * phase_yy == NULL it IS sf_tess_fill, bit for bit (sf_tess_fill is this
+ * call).  Every smoothing path serves: fused up to smooth_pix = 6, sf_smooth
+ * above (ring_slots >= S); labels outside 1..D give NaN (1 / 0 under the
+ * scrub) in all four planes.
+ */
+int sf_tess_fill_pol(sf_ctx* ctx, const int32_t* labels, int nx, int ny,
+                     const double* phase, const double* phase_yy,
+                     const double* amp_xx, const double* amp_yy, int D, int64_t S,
+                     float* out, int64_t ring_slots, double smooth_pix,
+                     unsigned flags);
 
 /*
  * The Gaussian smoothing of Screen.write (screen.py:353-362:

@@ -800,6 +800,29 @@ int sf_kl_eval_values(sf_ctx* ctx, const double* coef, int64_t S, float* out,
   return sf::launch_eval_values(ctx, coef, S, out, ring, flags);
 }
 
+int sf_kl_eval_pol(sf_ctx* ctx, const double* phase_xx, const double* phase_yy,
+                   const double* amp_xx, const double* amp_yy, int64_t S, float* out,
+                   int64_t ring, unsigned flags) {
+  SF_REQUIRE(ctx, SF_EINVAL, "sf_kl_eval_pol: NULL context");
+  SF_REQUIRE(ctx->D > 0 && ctx->n_pix > 0 && ctx->d_cfrag, SF_EINVAL,
+             "sf_kl_eval_pol: call sf_set_grid first");
+  SF_REQUIRE(phase_xx && phase_yy, SF_EINVAL,
+             "sf_kl_eval_pol: both phase coefficient sets are required");
+  SF_REQUIRE((amp_xx == nullptr) == (amp_yy == nullptr), SF_EINVAL,
+             "sf_kl_eval_pol: give both amplitude coefficient sets or neither");
+  SF_REQUIRE(out && S >= 0 && ring >= 1, SF_EINVAL, "sf_kl_eval_pol: bad argument");
+  SF_REQUIRE((reinterpret_cast<uintptr_t>(out) & 3) == 0, SF_EINVAL,
+             "sf_kl_eval_pol: output not 4-byte aligned");
+  SF_REQUIRE((flags & ~(SF_EVAL_NAN_SCRUB | SF_EVAL_FAST_SINCOS | SF_EVAL_NT_STORES |
+                        SF_EVAL_BIG_ENDIAN)) == 0,
+             SF_EINVAL,
+             "sf_kl_eval_pol: flags other than SF_EVAL_NAN_SCRUB, SF_EVAL_FAST_SINCOS, "
+             "SF_EVAL_NT_STORES and SF_EVAL_BIG_ENDIAN");
+  if (S == 0) return SF_OK;
+  SF_HIP(hipSetDevice(ctx->device));
+  return sf::launch_eval_pol(ctx, phase_xx, phase_yy, amp_xx, amp_yy, S, out, ring, flags);
+}
+
 int sf_set_tec_freqs(sf_ctx* ctx, const double* rad_per_tecu, const int* tec_index,
                      int F, int F_tec) {
   SF_REQUIRE(ctx, SF_EINVAL, "sf_set_tec_freqs: NULL context");
@@ -929,6 +952,15 @@ int sf_tess_fill(sf_ctx* ctx, const int32_t* labels, int nx, int ny,
                  const double* phase, const double* amp_xx,
                  const double* amp_yy, int D, int64_t S, float* out,
                  int64_t ring, double smooth_pix, unsigned flags) {
+  return sf_tess_fill_pol(ctx, labels, nx, ny, phase, nullptr, amp_xx, amp_yy, D, S, out, ring,
+                          smooth_pix, flags);
+}
+
+// (the messages name sf_tess_fill: this is that call with a second phase array)
+int sf_tess_fill_pol(sf_ctx* ctx, const int32_t* labels, int nx, int ny,
+                     const double* phase, const double* phase_yy, const double* amp_xx,
+                     const double* amp_yy, int D, int64_t S, float* out,
+                     int64_t ring, double smooth_pix, unsigned flags) {
   SF_REQUIRE(ctx && labels && phase && out, SF_EINVAL, "sf_tess_fill: NULL argument");
   SF_REQUIRE(nx >= 1 && ny >= 1 && D >= 1 && D <= SF_MAX_EVAL_DIR && S >= 0 && ring >= 1 &&
                  ring <= INT32_MAX,
@@ -942,13 +974,14 @@ int sf_tess_fill(sf_ctx* ctx, const int32_t* labels, int nx, int ny,
   if (rc != SF_OK) return rc;
   if (R <= sf::kTessMaxR)
     return (ctx->tess_tile ? sf::launch_tess_tile : sf::launch_tess)(
-        ctx, labels, nx, ny, phase, amp_xx, amp_yy, D, S, out, ring, ctx->d_gw, R, flags);
+        ctx, labels, nx, ny, phase, phase_yy, amp_xx, amp_yy, D, S, out, ring, ctx->d_gw, R,
+        flags);
   // wider Gaussians: gather unsmoothed and unscrubbed, then the separable
   // passes of sf_smooth (scrub / byte swap after smoothing, as the
   // reference); every slot needs its own cube for that
   SF_REQUIRE(ring >= S, SF_EINVAL,
              "sf_tess_fill: smooth_pix > 6 needs ring_slots >= S");
-  rc = sf::launch_tess(ctx, labels, nx, ny, phase, amp_xx, amp_yy, D, S, out,
+  rc = sf::launch_tess(ctx, labels, nx, ny, phase, phase_yy, amp_xx, amp_yy, D, S, out,
                        ring, ctx->d_gw, 0, 0u);
   if (rc != SF_OK) return rc;
   return sf::launch_smooth(ctx, out, nx, ny, S * 4, ctx->d_gw, R, flags);

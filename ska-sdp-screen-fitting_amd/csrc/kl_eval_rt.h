@@ -1,6 +1,6 @@
 // kl_eval_rt.h -- what the evaluation kernels that take the k-step count at
 // run time share: the k-loop (kl_eval_wide.hip, kl_values.hip, kl_points.hip),
-// the Jones epilogue of one accumulator row (wide, points) and the launch
+// the Jones epilogue of one accumulator row (wide, points; pol) and the launch
 // geometry of the pixel-block walk (wide, values).  The device parts are
 // inlined into the kernel that calls them: each kernel stays in its own unit,
 // under that unit's compiler flags (csrc/Makefile).  The functors a kernel
@@ -16,7 +16,10 @@ constexpr int kMaxSets = 3;  // coefficient sets of a contraction: phase, XX, YY
 
 // The contraction of 16 slots with NT 16-column B tiles over ks_pad k-steps,
 // KC per trip (ks_pad % KC == 0), for NSET coefficient sets that share the B
-// operand (1, or 3 for gain in the order phase, XX, YY).  row[s] is the
+// operand (1, 3 for gain in the order phase, XX, YY, or 2 / 4 for polarized
+// phases: phase XX, phase YY, amplitude XX, YY -- kl_eval_pol.hip, whose row
+// array has its own length kPolSets: with kMaxSets itself at 4 the code objects
+// of kl_tec.o and kl_points.o moved, profiles/README.md).  row[s] is the
 // lane's coefficient row (a clamped one when !srow), dl = l >> 4 its
 // direction within a k-step, bfrag(k, t) the lane's B fragment of k-step k,
 // tile t.  The raw fragments of a trip are unconditional loads of clamped
@@ -25,12 +28,12 @@ constexpr int kMaxSets = 3;  // coefficient sets of a contraction: phase, XX, YY
 // masked when used; the next trip's loads are issued before this trip's
 // v_mfma_f64_16x16x4_f64 (the last trip reloads its own: no branch).  Only
 // the accumulator tiles stay in registers across the loop.
-template <int KC, int NT, int NSET, typename Scaled, typename BFrag>
+template <int KC, int NT, int NSET, typename Scaled, typename BFrag, int NROW>
 __device__ __forceinline__ void rt_contract(v4d (&acc)[NSET][NT],
-                                            const double* const (&row)[kMaxSets],
+                                            const double* const (&row)[NROW],
                                             bool srow, int D, int ks_pad, int dl,
                                             Scaled scaled, BFrag bfrag) {
-  static_assert(NSET >= 1 && NSET <= kMaxSets, "phase, or phase + XX + YY");
+  static_assert(NSET >= 1 && NSET <= NROW, "a row per coefficient set");
 #pragma unroll
   for (int s = 0; s < NSET; ++s)
 #pragma unroll
@@ -129,9 +132,65 @@ __device__ __forceinline__ void jones_row(float (&pv)[4][NT],
   }
 }
 
+// jones_row for polarized phases (kl_eval_pol.hip): sets 0 / 1 are the XX / YY
+// phases in turns, sets 2 / 3 (GAIN) the XX / YY log-amplitudes.  Per pixel two
+// reductions and two sincos, pol p into planes 2 p, 2 p + 1 with jones_row's
+// arithmetic, so equal XX and YY phases give jones_row's bits.  The scrub is
+// jones_row's too, per plane pair: a NaN of one pol leaves the other's planes
+// alone.
+template <bool FAST, bool GAIN, int NT>
+__device__ __forceinline__ void jones_row_pol(float (&pv)[4][NT],
+                                              const v4d (&acc)[GAIN ? 4 : 2][NT], int r,
+                                              bool scrub) {
+  float fr[2][NT];
+  if constexpr (FAST) {
+#pragma unroll
+    for (int p = 0; p < 2; ++p) {
+      double rv[NT];
+#pragma unroll
+      for (int t = 0; t < NT; ++t) rv[t] = acc[p][t][r];
+      rev_reduce_n<NT>(fr[p], rv, !GAIN && scrub);
+    }
+  }
+  constexpr bool kScrubValues = GAIN || !FAST;
+  bool bad = false;
+#pragma unroll
+  for (int t = 0; t < NT; ++t) {
+#pragma unroll
+    for (int p = 0; p < 2; ++p) {
+      float sn, cs;
+      if constexpr (FAST) sincos_rev(fr[p][t], sn, cs);
+      else sincos_rev_f64(acc[p][t][r], sn, cs);
+      if constexpr (GAIN) {
+        if constexpr (FAST) {
+          const float a = amp2f(acc[2 + p][t][r]);
+          pv[2 * p][t] = a * cs;
+          pv[2 * p + 1][t] = a * sn;
+        } else {
+          // reference: A (fp64) * cos (fp64), one cast to float32
+          const double a = exp10(acc[2 + p][t][r]);
+          pv[2 * p][t] = (float)(a * (double)cs);
+          pv[2 * p + 1][t] = (float)(a * (double)sn);
+        }
+      } else {
+        pv[2 * p][t] = cs;
+        pv[2 * p + 1][t] = sn;
+      }
+      if (kScrubValues) bad |= __builtin_isunordered(pv[2 * p][t], pv[2 * p + 1][t]);
+    }
+  }
+  if (kScrubValues && scrub && __builtin_amdgcn_ballot_w64(bad) != 0) {
+#pragma unroll
+    for (int t = 0; t < NT; ++t)
+#pragma unroll
+      for (int q = 0; q < 4; ++q)
+        if (isnan(pv[q][t])) pv[q][t] = (q & 1) ? 0.0f : 1.0f;
+  }
+}
+
 // Launch geometry of the kernels whose workgroups walk (64-pixel block, chunk
 // of ring groups) items with the block's Cpix fragments in LDS, for a trip of
-// kc k-steps (kl_eval_wide_kernel, kl_values_kernel)
+// kc k-steps (kl_eval_wide_kernel, kl_values_kernel, kl_eval_pol_kernel)
 struct BlockWalkLaunch {
   int ks_pad, groups;
   size_t lds;    // ks_pad x 2 KiB <= 64 KiB

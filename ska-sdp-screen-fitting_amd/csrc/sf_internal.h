@@ -310,6 +310,11 @@ int launch_eval(sf_ctx* ctx, const double* coef, const double* cxx,
 int launch_eval_wide(sf_ctx* ctx, const double* coef, const double* cxx,
                      const double* cyy, int64_t S, float* out, int64_t ring,
                      unsigned flags, unsigned* sums);
+// polarized phases (XX / YY), amplitudes both given or both null, any D
+// (kl_eval_pol.hip)
+int launch_eval_pol(sf_ctx* ctx, const double* ph_xx, const double* ph_yy,
+                    const double* amp_xx, const double* amp_yy, int64_t S, float* out,
+                    int64_t ring, unsigned flags);
 // screen values on the pixel grid, any D (kl_values.hip)
 int launch_eval_values(sf_ctx* ctx, const double* coef, int64_t S, float* out,
                        int64_t ring, unsigned flags);
@@ -325,12 +330,14 @@ int launch_eval_points(sf_ctx* ctx, const double* coef, const double* cxx,
                        const double* cyy, int64_t S, float* planes, unsigned flags);
 int launch_eval_point_values(sf_ctx* ctx, const double* coef, int64_t S,
                              double* values);
+// phase_yy: the YY phases of a polarized table, or null (planes 2 / 3 take
+// the phase of planes 0 / 1)
 int launch_tess(sf_ctx* ctx, const int32_t* labels, int nx, int ny,
-                const double* phase, const double* amp_xx,
+                const double* phase, const double* phase_yy, const double* amp_xx,
                 const double* amp_yy, int D, int64_t S, float* out,
                 int64_t ring, const double* d_w, int R, unsigned flags);
 int launch_tess_tile(sf_ctx* ctx, const int32_t* labels, int nx, int ny,
-                const double* phase, const double* amp_xx,
+                const double* phase, const double* phase_yy, const double* amp_xx,
                 const double* amp_yy, int D, int64_t S, float* out,
                 int64_t ring, const double* d_w, int R, unsigned flags);
 int launch_smooth(sf_ctx* ctx, float* cube, int nx, int ny, int64_t n_img,

@@ -5,6 +5,7 @@
 // (screen.py:353-362):
 //   out[s][p][y][x] = g(value_p[s][label[y][x] - 1]),  value_p in
 //     {A_xx cos(phi), A_xx sin(phi), A_yy cos(phi), A_yy sin(phi)}
+// (sf_tess_fill_pol: phi_yy in the last two, for tables with polarized phases)
 // with g = identity or the separable Gaussian (axis y then axis x, float32
 // between the passes, 'reflect' borders, scipy's symmetric-kernel summation
 // order in float64).  sf_tess_fill runs a per-slot value-table pass and then
@@ -61,7 +62,7 @@ __device__ __forceinline__ float scrub_swap(float x, int p, bool scrub, bool be)
 }
 
 // The NP smoothed planes of a pixel (NP = 2: planes 2 / 3 repeat planes 0 / 1
-// -- no YY amplitude, A_yy = A_xx -- so only two are smoothed and each is
+// -- no YY amplitude or phase, A_yy = A_xx -- so only two are smoothed and each is
 // stored twice): fp64 sums, float32 between the passes like scipy's
 // intermediate image
 template <int NP>
@@ -80,8 +81,8 @@ __device__ __forceinline__ tess_acc_t<NP> widen(const V& v) {
 template <int TC>
 __global__ __launch_bounds__(256) void kl_tess_kernel(
     const int32_t* __restrict__ labels, int nx, int ny,
-    const double* __restrict__ phase, const double* __restrict__ amp_xx,
-    const double* __restrict__ amp_yy, int D, int64_t S,
+    const double* __restrict__ phase, const double* __restrict__ phase_yy,
+    const double* __restrict__ amp_xx, const double* __restrict__ amp_yy, int D, int64_t S,
     float* __restrict__ out, int64_t ring, const double* __restrict__ gw,
     int R, unsigned flags) {
 #pragma clang fp contract(off)
@@ -117,12 +118,14 @@ __global__ __launch_bounds__(256) void kl_tess_kernel(
       const int d = threadIdx.x;
       double sn, cn;
       sincos(phase[s * D + d], &sn, &cn);
+      double sny = sn, cny = cn;  // polarized phases: planes 2 / 3 take YY's
+      if (phase_yy) sincos(phase_yy[s * D + d], &sny, &cny);
       const double ax = amp_xx ? amp_xx[s * D + d] : 1.0;
       const double ay = amp_yy ? amp_yy[s * D + d] : ax;
       table[d * 4 + 0] = (float)(ax * cn);
       table[d * 4 + 1] = (float)(ax * sn);
-      table[d * 4 + 2] = (float)(ay * cn);
-      table[d * 4 + 3] = (float)(ay * sn);
+      table[d * 4 + 2] = (float)(ay * cny);
+      table[d * 4 + 3] = (float)(ay * sny);
     }
     __syncthreads();
     float v[4];
@@ -189,8 +192,8 @@ constexpr int kGatherWavesAuto = 16;   // waves per workgroup (SF_OPT_TESS_WAVES
 constexpr int kGatherSlotsAuto = 16;   // slots per work item (SF_OPT_TESS_SLOTS)
 
 __global__ __launch_bounds__(256) void kl_tess_table_kernel(
-    const double* __restrict__ phase, const double* __restrict__ amp_xx,
-    const double* __restrict__ amp_yy, int D, int64_t S,
+    const double* __restrict__ phase, const double* __restrict__ phase_yy,
+    const double* __restrict__ amp_xx, const double* __restrict__ amp_yy, int D, int64_t S,
     tess_v4f* __restrict__ tab, unsigned flags) {
   const int DT = D + 1;
   const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -202,12 +205,14 @@ __global__ __launch_bounds__(256) void kl_tess_table_kernel(
     const int64_t i = s * D + d;
     double sn, cn;
     sincos(phase[i], &sn, &cn);
+    double sny = sn, cny = cn;  // polarized phases: planes 2 / 3 take YY's
+    if (phase_yy) sincos(phase_yy[i], &sny, &cny);
     const double ax = amp_xx ? amp_xx[i] : 1.0;
     const double ay = amp_yy ? amp_yy[i] : ax;
     v[0] = (float)(ax * cn);
     v[1] = (float)(ax * sn);
-    v[2] = (float)(ay * cn);
-    v[3] = (float)(ay * sn);
+    v[2] = (float)(ay * cny);
+    v[3] = (float)(ay * sny);
   } else {
     v[0] = v[1] = v[2] = v[3] = __builtin_nanf("");
   }
@@ -756,7 +761,7 @@ constexpr int compiled_radius(TessKind kind, int NP, int TC, int R) {
 struct TessCall {
   sf_ctx* ctx;
   const int32_t* labels;
-  const double *phase, *amp_xx, *amp_yy;  // [S][D]; amplitudes or null
+  const double *phase, *phase_yy, *amp_xx, *amp_yy;  // [S][D]; all but phase or null
   const double* d_w;                      // Gaussian weights of radius R
   float* out;
   int nx, ny, D, R;  // R = 0: unsmoothed
@@ -801,13 +806,14 @@ static TessPlan plan_tess(const TessCall& c) {
     return p;
   }
   // smoothing: the interior-lookup kernel or the wide-tile kernel
-  // (SF_OPT_TESS_BOX; auto: interior lookups for four planes at R <= 5, where
+  // (SF_OPT_TESS_BOX; auto: interior lookups for four planes -- a YY amplitude
+  // or a YY phase -- at R <= 5, where
   // the wide-tile kernel is fp64-VALU-bound -- sigma 0.25 / 0.5 / 0.75 / 1 /
   // 1.25 px: 0.66 / 0.51 / 0.42 / 0.35 / 0.31 -> 0.73 / 0.73 / 0.59 / 0.44 /
   // 0.37 of 8 TB/s; with two planes, or at R = 8, the wide-tile kernel's
   // sliding windows win: profiles/round3p_tess_box_sweep.txt)
   const bool box = c.R <= kBoxMaxR &&
-                   (ctx->tess_box == 1 || (ctx->tess_box < 0 && c.amp_yy && c.R <= 5));
+                   (ctx->tess_box == 1 || (ctx->tess_box < 0 && (c.amp_yy || c.phase_yy) && c.R <= 5));
   p.kind = box ? kTessBox : kTessSmooth;
   p.chunk = box ? kBoxSlots : kSmSlots;
   const int rows = box ? kBoxTH : smooth_rows(c.R);  // the kernel's tile rows
@@ -859,14 +865,17 @@ static void launch_fill(const TessCall& c, const TessPlan& p, const tess_v4f* ta
             launch(kl_tess_smooth_kernel<RT, NP, TC>);
         });
       },
-      p.kind == kTessBox, c.amp_yy != nullptr, c.D + 1 > kTabCap);
+      // four planes as soon as planes 2 / 3 differ from planes 0 / 1
+      p.kind == kTessBox, c.amp_yy != nullptr || c.phase_yy != nullptr, c.D + 1 > kTabCap);
 }
 
 int launch_tess(sf_ctx* ctx, const int32_t* labels, int nx, int ny,
-                const double* phase, const double* amp_xx,
+                const double* phase, const double* phase_yy, const double* amp_xx,
                 const double* amp_yy, int D, int64_t S, float* out,
                 int64_t ring, const double* d_w, int R, unsigned flags) {
-  const TessCall c{ctx, labels, phase, amp_xx, amp_yy, d_w, out, nx, ny, D, R, S, ring, flags};
+  const TessCall c{ctx,    labels, phase, phase_yy, amp_xx, amp_yy, d_w,
+                   out,    nx,     ny,    D,        R,      S,      ring,
+                   flags};
   const TessPlan p = plan_tess(c);
   // the value table of at most `per` slots (<= 256 MiB of scratch, a multiple
   // of the chunk) in the context's scratch buffer
@@ -881,6 +890,7 @@ int launch_tess(sf_ctx* ctx, const int32_t* labels, int nx, int ny,
     const int64_t Sb = S - b < per ? S - b : per;
     hipLaunchKernelGGL(kl_tess_table_kernel, dim3((unsigned)((Sb * DT + 255) / 256)),
                        dim3(256), 0, ctx->stream, phase + b * D,
+                       phase_yy ? phase_yy + b * D : nullptr,
                        amp_xx ? amp_xx + b * D : nullptr,
                        amp_yy ? amp_yy + b * D : nullptr, D, Sb, tab, p.tab_flags);
     SF_HIP(hipGetLastError());
@@ -893,7 +903,7 @@ int launch_tess(sf_ctx* ctx, const int32_t* labels, int nx, int ny,
 // The round-1 fused tile kernel (16 x 16 tiles, table built per tile), kept
 // for cross-checks (SF_OPT_TESS_TILE): same bits as launch_tess.
 int launch_tess_tile(sf_ctx* ctx, const int32_t* labels, int nx, int ny,
-                     const double* phase, const double* amp_xx,
+                     const double* phase, const double* phase_yy, const double* amp_xx,
                      const double* amp_yy, int D, int64_t S, float* out,
                      int64_t ring, const double* d_w, int R, unsigned flags) {
   const int tiles = ((nx + kTT - 1) / kTT) * ((ny + kTT - 1) / kTT);
@@ -902,7 +912,8 @@ int launch_tess_tile(sf_ctx* ctx, const int32_t* labels, int nx, int ny,
       [&](auto WIDE) {
         hipLaunchKernelGGL(kl_tess_kernel<tab_cap(decltype(WIDE)::value)>,
                            dim3(tiles, (unsigned)chunks), dim3(256), 0, ctx->stream, labels, nx,
-                           ny, phase, amp_xx, amp_yy, D, S, out, ring, d_w, R, flags);
+                           ny, phase, phase_yy, amp_xx, amp_yy, D, S, out, ring, d_w, R,
+                           flags);
       },
       D + 1 > kTabCap);
   SF_HIP(hipGetLastError());

@@ -79,6 +79,7 @@ EXPORTED = (
     "sf_set_points", "sf_kl_eval_points", "sf_kl_eval_point_values",
     "sf_kl_eval_values",
     "sf_set_tec_freqs", "sf_kl_eval_tec",
+    "sf_kl_eval_pol", "sf_tess_fill_pol",
 )
 
 
@@ -173,6 +174,10 @@ def load_library(path=None):
             "sf_kl_eval_values": ([vp, vp, i64, vp, i64, ctypes.c_uint], c_int),
             "sf_set_tec_freqs": ([vp, vp, vp, c_int, c_int], c_int),
             "sf_kl_eval_tec": ([vp, vp, vp, i64, c_int, vp, ctypes.c_uint], c_int),
+            "sf_kl_eval_pol": ([vp, vp, vp, vp, vp, i64, vp, i64, ctypes.c_uint],
+                               c_int),
+            "sf_tess_fill_pol": ([vp, vp, c_int, c_int, vp, vp, vp, vp, c_int, i64,
+                                  vp, i64, c_dbl, ctypes.c_uint], c_int),
         }
         for name, (args, res) in sig.items():
             fn = getattr(lib, name)
@@ -428,6 +433,24 @@ class Context:
             self._dev(out, np.float32, self._out_numel(S, ring) // 4, "out"), ring,
             int(flags)), "sf_kl_eval_values")
 
+    def eval_pol(self, phase_xx, phase_yy, S, out, ring_slots=None, amp_xx=None,
+                 amp_yy=None,
+                 flags=SF_EVAL_NAN_SCRUB | SF_EVAL_FAST_SINCOS | SF_EVAL_NT_STORES):
+        """sf_kl_eval_pol: Jones planes [min(S, ring), 4, ny, nx] float32 of a
+        diagonal gain with polarized phases: planes 0 / 1 take cos / sin of the
+        ``phase_xx`` screens, planes 2 / 3 of the ``phase_yy`` screens, times
+        10 ** the ``amp_xx`` / ``amp_yy`` screens when both are given (all
+        device [S, D] float64)."""
+        ring = max(int(S if ring_slots is None else ring_slots), 1)
+        n = int(S) * self.D
+        _check(self.lib.sf_kl_eval_pol(
+            self.h, self._dev(phase_xx, np.float64, n, "phase_xx"),
+            self._dev(phase_yy, np.float64, n, "phase_yy"),
+            self._dev(amp_xx, np.float64, n, "amp_xx"),
+            self._dev(amp_yy, np.float64, n, "amp_yy"), int(S),
+            self._dev(out, np.float32, self._out_numel(S, ring), "out"), ring,
+            int(flags)), "sf_kl_eval_pol")
+
     def set_tec_freqs(self, rad_per_tecu, tec_index=None, n_tec_freq=None):
         """sf_set_tec_freqs: bind the F output channels of ``eval_tec``.
         Channel f renders ``rad_per_tecu[f]`` (= tec_to_phase / nu_f) times the
@@ -543,7 +566,9 @@ class Context:
 
     def tess_fill(self, labels, nx, ny, phase, D, S, out, ring_slots=None,
                   amp_xx=None, amp_yy=None, smooth_pix=0.0,
-                  flags=SF_EVAL_NAN_SCRUB):
+                  flags=SF_EVAL_NAN_SCRUB, phase_yy=None):
+        """sf_tess_fill; with ``phase_yy`` (polarized phases: planes 2 / 3
+        take its cos / sin) sf_tess_fill_pol."""
         ring = max(int(S if ring_slots is None else ring_slots), 1)
         n = int(S) * int(D)
         if hasattr(labels, "min") and labels.numel():
@@ -560,9 +585,10 @@ class Context:
                 if lo < 1 or hi > int(D):
                     raise ValueError(f"labels: values {lo}..{hi} outside 1..{D}")
                 self._labels_ok = (weakref.ref(labels), key)
-        _check(self.lib.sf_tess_fill(
+        _check(self.lib.sf_tess_fill_pol(
             self.h, self._dev(labels, np.int32, int(nx) * int(ny), "labels"),
             int(nx), int(ny), self._dev(phase, np.float64, n, "phase"),
+            self._dev(phase_yy, np.float64, n, "phase_yy"),
             self._dev(amp_xx, np.float64, n, "amp_xx"),
             self._dev(amp_yy, np.float64, n, "amp_yy"), int(D), int(S),
             self._dev(out, np.float32, min(int(S), ring) * 4 * int(nx) * int(ny), "out"),

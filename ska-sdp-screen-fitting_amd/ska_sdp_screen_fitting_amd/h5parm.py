@@ -14,7 +14,9 @@ Storage backends:
   ``/<solset>/source`` compound tables;
 * ``.npz`` produced by ``tools/h5parm_to_npz.py``:
   keys ``val weight times freqs dir_names ant_names dir_radec ant_pos``
-  (+ optional ``soltab``/``solset`` names and ``pol``/``amp_*`` arrays).
+  (+ optional ``soltab``/``solset`` names and ``amp_*`` arrays); ``val`` /
+  ``weight`` are [time, freq, ant, dir] or, for polarized phases,
+  [time, freq, ant, dir, pol] with the pol names in ``pol`` (default XX, YY).
 
 Unlike the reference, an H5parm opened for the KL fit is never mutated: the
 fitted screen soltabs live in memory (the reference writes them into the
@@ -130,9 +132,20 @@ class H5parm:
                 np.array([str(s) for s in z["ant_names"]]),
                 np.array([str(s) for s in z["dir_names"]])]
         name = str(z["soltab"]) if "soltab" in z else "phase000"
-        ss.soltabs[name] = Soltab(name, "phase", axes, vals,
-                                  np.asarray(z["val"], np.float64),
-                                  np.asarray(z["weight"], np.float32), solset=ss)
+        val = np.asarray(z["val"], np.float64)
+        weight = np.asarray(z["weight"], np.float32)
+        if val.shape != weight.shape or val.ndim not in (4, 5):
+            raise ValueError(f"{path}: val {val.shape} / weight {weight.shape}, "
+                             "expected equal [time, freq, ant, dir(, pol)] arrays")
+        paxes, pvals = axes, vals
+        if val.ndim == 5:
+            # polarized phases (a diagonal-mode solve): [time, freq, ant, dir, pol]
+            pol = [str(s) for s in z["pol"]] if "pol" in z else ["XX", "YY"]
+            if len(pol) != val.shape[4]:
+                raise ValueError(f"{path}: {len(pol)} pol names for a pol axis "
+                                 f"of length {val.shape[4]}")
+            paxes, pvals = axes + ["pol"], vals + [np.array(pol)]
+        ss.soltabs[name] = Soltab(name, "phase", paxes, pvals, val, weight, solset=ss)
         if "amp_val" in z:
             aname = name.replace("phase", "amplitude")
             aaxes = axes + ["pol"]

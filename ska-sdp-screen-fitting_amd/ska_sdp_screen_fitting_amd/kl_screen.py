@@ -22,7 +22,7 @@ from . import stationscreen
 from ._lib import (SF_EVAL_BIG_ENDIAN, SF_EVAL_FAST_SINCOS, SF_EVAL_NAN_SCRUB,
                    SF_EVAL_NT_STORES, SF_MAX_DIR, SF_MAX_POINTS, Context)
 from .h5parm import H5parm, get_reference_station
-from .screen import Screen
+from .screen import Screen, canonical_axes, phase_pols
 
 # NaN scrub (screen.py:368-378) + exact fp64 reduction of the phase in
 # revolutions / hardware fp32 sincos + streaming stores
@@ -161,6 +161,35 @@ class KLEvaluator:
             self.ctx.eval_gain(coef_dev, xx_dev, yy_dev, S, out_dev, S, flags)
         return out_dev
 
+    def eval_pol_device(self, xx_dev, yy_dev, out_dev=None, amp_xx_dev=None,
+                        amp_yy_dev=None, flags=DEFAULT_FLAGS):
+        """Polarized phases (``sf_kl_eval_pol``): the XX and YY phase
+        coefficients (device [S, D] each), and optionally the XX and YY
+        log10-amplitude coefficients (both or neither) -> device
+        [S, 4, ny, nx]: planes 0 / 1 from XX, planes 2 / 3 from YY."""
+        torch = self.torch
+        S = xx_dev.shape[0]
+        if out_dev is None:
+            out_dev = torch.empty((S, 4, self.ny, self.nx), dtype=torch.float32,
+                                  device=self.dev)
+        with torch.cuda.device(self.dev):
+            self.ctx.set_stream(torch.cuda.current_stream(self.dev).cuda_stream)
+            self.ctx.eval_pol(xx_dev, yy_dev, S, out_dev, S, amp_xx_dev, amp_yy_dev,
+                              flags)
+        return out_dev
+
+    def eval_pol_host(self, coef_xx, coef_yy, amp_xx=None, amp_yy=None,
+                      flags=DEFAULT_FLAGS):
+        """XX / YY phase coefficients (and optional log10-amplitude coefs):
+        host [..., D] -> host float32 [..., 4, ny, nx]."""
+        coef_xx = np.asarray(coef_xx)
+        lead = coef_xx.shape[:-1]
+        out = self.eval_pol_device(
+            self._upload(coef_xx), self._upload(coef_yy),
+            amp_xx_dev=None if amp_xx is None else self._upload(amp_xx),
+            amp_yy_dev=None if amp_yy is None else self._upload(amp_yy), flags=flags)
+        return out.cpu().numpy().reshape(lead + (4, self.ny, self.nx))
+
     def values_device(self, coef_dev, out_dev=None, flags=0):
         """coef_dev: device [S, D] float64 -> device [S, ny, nx] float32, the
         screen values themselves in the coefficients' units (``sf_kl_eval_values``:
@@ -294,13 +323,18 @@ class KLScreen(Screen):
         """Fit screens to the input solutions (kl_screen.py:61-155): phases
         with per-station orders referenced to a central station; for gain
         solutions also the XX / YY log10 amplitudes (order
-        min(12, max(3, round(D / 2))), 3 iterations, no order scaling)."""
+        min(12, max(3, round(D / 2))), 3 iterations, no order scaling).  A
+        phase soltab with a ``pol`` axis of length 2 (XX, YY: a diagonal-mode
+        solve) is fitted per pol, as ``stationscreen.run`` does for any pol
+        axis: ``vals_ph`` is then [time, freq, ant, dir, 2] and ``pol_phases``
+        is set; length 1 is the scalar case, any other length a ValueError."""
         self._evaluators = {}  # a refit invalidates the evaluated basis
         self._sampler = None
         h5 = H5parm(self.input_h5parm_filename)
         solset = h5.get_solset(self.input_solset_name)
         soltab_ph = solset.get_soltab(self.input_phase_soltab_name)
         dirs = [str(d) for d in soltab_ph.dir]
+        self.pol_phases = phase_pols(soltab_ph) == 2
         if self.input_skymodel_filename is not None:
             patches = set(read_patch_names(self.input_skymodel_filename))
             missing = [d for d in dirs if d.strip("[]") not in patches]
@@ -323,7 +357,7 @@ class KLScreen(Screen):
             self.times_amp = np.asarray(sta.time)
             self.freqs_amp = np.asarray(sta.freq)
         st = solset.get_soltab("phase_screen000")
-        self.vals_ph = st.val
+        self.vals_ph = canonical_axes(st, st.val)
         self.times_ph = np.asarray(st.time)
         self.freqs_ph = np.asarray(st.freq)
         self.source_names = st.dir
@@ -372,15 +406,19 @@ class KLScreen(Screen):
         optional smoothing (screen.py:353-378), and so does ``write_chunk``.
         The values carry the float32 rounding of the FITS cube (Q12)."""
         del out_dir, ncpu
-        sl = np.s_[t_start_index:t_stop_index, freq_ind, stat_ind, :]
+        sl = np.s_[t_start_index:t_stop_index, freq_ind, stat_ind]
         coef = np.asarray(self.vals_ph)[sl]
         ev = self.evaluator(cellsize_deg)
         flags = DEFAULT_FLAGS & ~SF_EVAL_NAN_SCRUB
-        if self.phase_only:
-            return ev.eval_host(coef, flags=flags).astype(np.float64)
-        amp = np.asarray(self.vals_amp)[sl]
-        return ev.eval_host(coef, amp[..., 0], amp[..., 1],
-                            flags=flags).astype(np.float64)
+        amp = (None, None)
+        if not self.phase_only:
+            a = np.asarray(self.vals_amp)[sl]
+            amp = (a[..., 0], a[..., 1])
+        if self.pol_phases:
+            # planes 0 / 1 from the XX phase screens, 2 / 3 from the YY ones
+            return ev.eval_pol_host(coef[..., 0], coef[..., 1], amp[0], amp[1],
+                                    flags=flags).astype(np.float64)
+        return ev.eval_host(coef, amp[0], amp[1], flags=flags).astype(np.float64)
 
     def write_chunk(self, writer, g_start, g_stop, cellsize_deg, smooth_pix,
                     max_batch_bytes=1 << 30):
@@ -396,7 +434,12 @@ class KLScreen(Screen):
         row_bytes = n_f * n_a * per_slot
         rows = max(1, int(max_batch_bytes // row_bytes))
         rows = min(rows, g_stop - g_start)
-        coef = ev._upload(vals[g_start:g_stop])
+        if self.pol_phases:
+            coef = ev._upload(vals[g_start:g_stop, ..., 0])
+            coef_y = ev._upload(vals[g_start:g_stop, ..., 1])
+            c_xx = c_yy = None
+        else:
+            coef = ev._upload(vals[g_start:g_stop])
         if not self.phase_only:
             amp = np.asarray(self.vals_amp)[g_start:g_stop]
             c_xx, c_yy = ev._upload(amp[..., 0]), ev._upload(amp[..., 1])
@@ -412,7 +455,12 @@ class KLScreen(Screen):
                 # (screen.py:353-378 smooths, then replaces NaNs)
                 flags = DEFAULT_FLAGS | fin if smooth_pix <= 0 else \
                     DEFAULT_FLAGS & ~SF_EVAL_NAN_SCRUB
-                if self.phase_only:
+                if self.pol_phases:
+                    # 2 coefficient sets, 4 with the amplitudes
+                    ev.eval_pol_device(coef[s0:s1], coef_y[s0:s1], out,
+                                       None if c_xx is None else c_xx[s0:s1],
+                                       None if c_yy is None else c_yy[s0:s1], flags)
+                elif self.phase_only:
                     ev.eval_device(coef[s0:s1], out, flags)
                 else:
                     ev.eval_gain_device(coef[s0:s1], c_xx[s0:s1], c_yy[s0:s1],
@@ -444,7 +492,10 @@ class KLScreen(Screen):
         Returns float64 ``[t_stop - t_start, F, A, 4, P]`` -- the planes of
         ``make_matrix`` (raw, not NaN-scrubbed, float32 rounding) -- or, with
         ``values``, the phase screen itself ``[t_stop - t_start, F, A, P]`` in
-        the fit's units (fp64).  Runs in device batches of whole time rows of
+        the fit's units (fp64).  With polarized phases (``pol_phases``) the
+        positions are evaluated once per pol (two ``sf_kl_eval_points`` calls):
+        planes 0 / 1 are those of the XX screens, planes 2 / 3 of the YY ones,
+        and ``values`` carries a trailing pol axis ``[..., P, 2]``.  Runs in device batches of whole time rows of
         at most ``max_batch_bytes`` (coefficients + output), so the call's
         device footprint does not grow with the number of times."""
         ra = np.atleast_1d(np.asarray(ra_deg))
@@ -464,13 +515,16 @@ class KLScreen(Screen):
             y = gy[np.where(inside, iy, 0)]
         xy = np.stack([np.where(inside, x, 0.0), np.where(inside, y, 0.0)], axis=1)
         vals = np.asarray(self.vals_ph)
-        n_t, n_f, n_a, D = vals.shape
+        n_t, n_f, n_a, D = vals.shape[:4]
+        pols = 2 if self.pol_phases else 1
         t_stop = n_t if t_stop is None else min(int(t_stop), n_t)
         t_start = int(t_start)
         if not 0 <= t_start <= t_stop:
             raise ValueError(f"times [{t_start}, {t_stop}) outside 0..{n_t}")
         gain = not self.phase_only and not values
         shape = (t_stop - t_start, n_f, n_a) + ((n_pos,) if values else (4, n_pos))
+        if values and self.pol_phases:
+            shape += (2,)
         out = np.full(shape, np.nan)
         if t_stop == t_start or not inside.any():
             return out
@@ -481,22 +535,33 @@ class KLScreen(Screen):
             sel = live[p0:p0 + SF_MAX_POINTS]
             P = sel.size
             ev.set_points(xy[sel])
-            row_bytes = n_f * n_a * ((8 if values else 16) * P + 8 * D * (3 if gain else 1))
+            row_bytes = n_f * n_a * ((8 if values else 16) * P * pols +
+                                     8 * D * ((2 if gain else 0) + pols))
             rows = max(1, int(max_batch_bytes // row_bytes))
             for t0 in range(t_start, t_stop, rows):
                 t1 = min(t_stop, t0 + rows)
-                coef = ev._upload(vals[t0:t1])
-                if values:
-                    got = ev.sample_device(coef, values=True)
-                elif gain:
+                dst = out[t0 - t_start:t1 - t_start]
+                if gain:
                     amp = np.asarray(self.vals_amp)[t0:t1]
-                    got = ev.sample_device(coef, ev._upload(amp[..., 0]),
-                                           ev._upload(amp[..., 1]), flags=flags)
-                else:
-                    got = ev.sample_device(coef, flags=flags)
-                got = got.cpu().numpy().reshape((t1 - t0, n_f, n_a) + got.shape[1:])
-                out[t0 - t_start:t1 - t_start][..., sel] = got
-                del coef, got
+                    c_xx, c_yy = ev._upload(amp[..., 0]), ev._upload(amp[..., 1])
+                for pol in range(pols):
+                    coef = ev._upload(vals[t0:t1, ..., pol] if self.pol_phases
+                                      else vals[t0:t1])
+                    if values:
+                        got = ev.sample_device(coef, values=True)
+                    elif gain:
+                        got = ev.sample_device(coef, c_xx, c_yy, flags=flags)
+                    else:
+                        got = ev.sample_device(coef, flags=flags)
+                    got = got.cpu().numpy().reshape((t1 - t0, n_f, n_a) + got.shape[1:])
+                    if not self.pol_phases:
+                        dst[..., sel] = got
+                    elif values:
+                        dst[..., sel, pol] = got
+                    else:
+                        # the pol's own plane pair of its evaluation
+                        dst[..., 2 * pol:2 * pol + 2, sel] = got[..., 2 * pol:2 * pol + 2, :]
+                    del coef, got
         return out
 
     def patch_errors(self, cellsize_deg=None, max_batch_bytes=1 << 30):
@@ -506,7 +571,9 @@ class KLScreen(Screen):
         |screen at the direction's position - expected|, where expected is
         (a_xx cos phi, a_xx sin phi, a_yy cos phi, a_yy sin phi), phi the input
         phase minus that of the reference station of ``fit`` and a the input
-        amplitudes on the phase grid (1 for phase-only screens).  Input
+        amplitudes on the phase grid (1 for phase-only screens); with polarized
+        phases planes 0 / 1 are compared with the XX input phases and planes
+        2 / 3 with the YY ones, each referenced to the reference station.  Input
         entries with zero weight or a non-finite value are left out; a
         direction outside the image (``cellsize_deg`` given) or without any
         usable entry gives NaN.  Positions are those of the solset's source
@@ -517,11 +584,13 @@ class KLScreen(Screen):
             raise RuntimeError("patch_errors needs the input solutions: call "
                                "fit() or process() first")
         st = self.solset.get_soltab(self.input_phase_soltab_name)
-        names = st.get_axes_names()
-        order = [names.index(a) for a in ("time", "freq", "ant", "dir")]
-        val = np.transpose(np.asarray(st.val, np.float64), order)
-        wgt = np.transpose(np.asarray(st.weight), order)
-        n_t, n_f, n_a, D = val.shape
+        val = np.asarray(canonical_axes(st, st.val), np.float64)
+        wgt = canonical_axes(st, st.weight)
+        n_t, n_f, n_a, D = val.shape[:4]
+        if not self.pol_phases:
+            # one phase for both plane pairs: a pol axis of length 1 that views
+            # the scalar arrays twice
+            val, wgt = val[..., None], wgt[..., None]
         if not self.phase_only:
             sa = self.solset.get_soltab(self.input_amplitude_soltab_name)
             an = sa.get_axes_names()
@@ -555,18 +624,20 @@ class KLScreen(Screen):
             # position k is direction k's: the last axis of both arrays
             got = self.sample(ra, de, cellsize_deg, t0, t1,
                               max_batch_bytes=max_batch_bytes)
-            phi = val[t0:t1] - val[t0:t1, :, self.ref_ind:self.ref_ind + 1, :]
+            phi = val[t0:t1] - val[t0:t1, :, self.ref_ind:self.ref_ind + 1]
             use = (wgt[t0:t1] != 0) & np.isfinite(val[t0:t1])
             if self.phase_only:
                 axx = ayy = 1.0
             else:
                 axx, ayy = aval[t0:t1, ..., 0], aval[t0:t1, ..., 1]
                 use &= ((awgt[t0:t1, ..., 0] != 0) & (awgt[t0:t1, ..., 1] != 0) &
-                        np.isfinite(axx) & np.isfinite(ayy))
-            want = (axx * np.cos(phi), axx * np.sin(phi),
-                    ayy * np.cos(phi), ayy * np.sin(phi))
+                        np.isfinite(axx) & np.isfinite(ayy))[..., None]
+            px, py = phi[..., 0], phi[..., -1]  # the same array without pols
+            want = (axx * np.cos(px), axx * np.sin(px),
+                    ayy * np.cos(py), ayy * np.sin(py))
             for q in range(4):
-                diff = np.where(use, np.abs(got[:, :, :, q] - want[q]), -np.inf)
+                u = use[..., 0 if q < 2 else -1]
+                diff = np.where(u, np.abs(got[:, :, :, q] - want[q]), -np.inf)
                 err = np.maximum(err, diff.reshape(-1, D).max(axis=0))
         err[~inside | ~np.isfinite(err)] = np.nan
         return err

@@ -94,6 +94,32 @@ def resample_axis(src, vals, dst, axis, kind="nearest"):
                        fill_value="extrapolate")(dst)
 
 
+def phase_pols(soltab):
+    """Number of polarizations of a phase soltab as the screens render it: 0
+    without a ``pol`` axis or with one of length 1 (the scalar case), 2 for
+    (XX, YY) -- planes 0 / 1 of the cube then take the first pol's phase,
+    planes 2 / 3 the second's.  Any other length raises ValueError."""
+    names = soltab.get_axes_names()
+    if "pol" not in names:
+        return 0
+    n = np.shape(soltab.val)[names.index("pol")]
+    if n not in (1, 2):
+        raise ValueError(f"soltab {soltab.name!r}: axis 'pol' has length {n}; the "
+                         "a-term planes hold a diagonal gain (1 or 2 pols: XX, YY)")
+    return 0 if n == 1 else 2
+
+
+def canonical_axes(soltab, arr):
+    """``arr`` (the soltab's val or weight) as [time, freq, ant, dir(, pol)],
+    a ``pol`` axis of length 1 dropped."""
+    names = soltab.get_axes_names()
+    order = [names.index(a) for a in ("time", "freq", "ant", "dir")]
+    if "pol" in names:
+        order.append(names.index("pol"))
+    arr = np.transpose(np.asarray(arr), order)
+    return arr[..., 0] if arr.ndim == 5 and arr.shape[4] == 1 else arr
+
+
 class Screen:
     """Master class for a-term screens (screen.py:19)."""
 
@@ -118,6 +144,9 @@ class Screen:
         self.times_ph = []
         self.vals_amp = None
         self.vals_ph = None
+        # True: vals_ph is [time, freq, ant, dir, 2], the XX and YY phases of
+        # a table with polarized phases (phase_pols)
+        self.pol_phases = False
         self.freqs_amp = None
         self.freqs_ph = None
         self.station_names = None

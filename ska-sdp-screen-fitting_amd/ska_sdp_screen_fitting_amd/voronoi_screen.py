@@ -23,7 +23,7 @@ from scipy.spatial import Voronoi
 from . import fits, geometry
 from ._lib import SF_EVAL_BIG_ENDIAN, SF_EVAL_NAN_SCRUB, private_context
 from .h5parm import H5parm, get_reference_station
-from .screen import Screen
+from .screen import Screen, canonical_axes, phase_pols
 
 
 def parse_angle(text, hours):
@@ -206,13 +206,19 @@ class VoronoiScreen(Screen):
     def fit(self):
         """Reference the phases to one station (voronoi_screen.py:57-102);
         gain solutions also keep the raw XX / YY amplitudes
-        [time, freq, ant, dir, pol] for interpolation."""
+        [time, freq, ant, dir, pol] for interpolation.  A phase soltab with a
+        ``pol`` axis of length 2 (XX, YY) is referenced per pol: ``vals_ph`` is
+        then [time, freq, ant, dir, 2] and ``pol_phases`` is set; length 1 is
+        the scalar case, any other length a ValueError."""
         h5 = H5parm(self.input_h5parm_filename)
         solset = h5.get_solset(self.input_solset_name)
         st = solset.get_soltab(self.input_phase_soltab_name)
         ref = get_reference_station(st, 10)
+        self.pol_phases = phase_pols(st) == 2
         vals = np.array(st.val, dtype=np.float64)
-        vals = vals - vals[:, :, ref:ref + 1, :]
+        if "pol" in st.get_axes_names():
+            vals = canonical_axes(st, vals)
+        vals = vals - vals[:, :, ref:ref + 1]
         self.vals_ph = vals
         self.times_ph = np.asarray(st.time)
         self.freqs_ph = np.asarray(st.freq)
@@ -269,9 +275,12 @@ class VoronoiScreen(Screen):
         return self._dev_cache
 
     def eval_device(self, ph_dev, out_dev, smooth_pix=0.0,
-                    flags=SF_EVAL_NAN_SCRUB, amp_xx=None, amp_yy=None):
+                    flags=SF_EVAL_NAN_SCRUB, amp_xx=None, amp_yy=None,
+                    phase_yy=None):
         """device [S, D] referenced phases (and optional XX / YY amplitudes,
-        device [S, D]) -> device [S, 4, ny, nx]."""
+        device [S, D]) -> device [S, 4, ny, nx].  ``phase_yy``: the YY phases
+        of a table with polarized phases (planes 2 / 3; ``ph_dev`` is then
+        XX's)."""
         import torch
         dev, lab = self._device()
         ny, nx = self.data_rasertize_template.shape
@@ -288,7 +297,8 @@ class VoronoiScreen(Screen):
                 stream.wait_event(busy)
             ctx.set_stream(stream.cuda_stream)
             ctx.tess_fill(lab, nx, ny, ph_dev, D, S, out_dev, amp_xx=amp_xx,
-                          amp_yy=amp_yy, smooth_pix=smooth_pix, flags=flags)
+                          amp_yy=amp_yy, smooth_pix=smooth_pix, flags=flags,
+                          phase_yy=phase_yy)
             ctx.tess_busy = torch.cuda.Event()
             ctx.tess_busy.record(stream)
         return out_dev
@@ -300,9 +310,10 @@ class VoronoiScreen(Screen):
         return torch.from_numpy(a.reshape(-1, a.shape[-1])).to(dev)
 
     def eval_host(self, phase, smooth_pix=0.0, amp_xx=None, amp_yy=None,
-                  flags=SF_EVAL_NAN_SCRUB):
-        """[..., D] referenced phases (optional amplitudes) -> float32
-        [..., 4, ny, nx] (gather + optional Gaussian smoothing) on the GPU."""
+                  flags=SF_EVAL_NAN_SCRUB, phase_yy=None):
+        """[..., D] referenced phases (optional amplitudes, optional YY
+        phases) -> float32 [..., 4, ny, nx] (gather + optional Gaussian
+        smoothing) on the GPU."""
         import torch
         dev, _ = self._device()
         lead = np.shape(phase)[:-1]
@@ -310,8 +321,10 @@ class VoronoiScreen(Screen):
         ph = self._upload(phase)
         axx = None if amp_xx is None else self._upload(amp_xx)
         ayy = None if amp_yy is None else self._upload(amp_yy)
+        pyy = None if phase_yy is None else self._upload(phase_yy)
         out = torch.empty((ph.shape[0], 4, ny, nx), dtype=torch.float32, device=dev)
-        self.eval_device(ph, out, smooth_pix, flags, amp_xx=axx, amp_yy=ayy)
+        self.eval_device(ph, out, smooth_pix, flags, amp_xx=axx, amp_yy=ayy,
+                         phase_yy=pyy)
         return out.cpu().numpy().reshape(lead + (4, ny, nx))
 
     def make_matrix(self, t_start_index, t_stop_index, freq_ind, stat_ind,
@@ -322,13 +335,15 @@ class VoronoiScreen(Screen):
         del ncpu
         if self.data_rasertize_template is None:
             self.make_rasertize_template(cellsize_deg, out_dir)
-        sl = np.s_[t_start_index:t_stop_index, freq_ind, stat_ind, :]
-        ph = self.vals_ph[sl]
+        sl = np.s_[t_start_index:t_stop_index, freq_ind, stat_ind]
+        ph, ph_yy = self.vals_ph[sl], None
+        if self.pol_phases:
+            ph, ph_yy = ph[..., 0], ph[..., 1]
         if self.phase_only:
-            return self.eval_host(ph, flags=0).astype(np.float64)
+            return self.eval_host(ph, flags=0, phase_yy=ph_yy).astype(np.float64)
         amp = np.asarray(self.vals_amp)[sl]
         return self.eval_host(ph, amp_xx=amp[..., 0], amp_yy=amp[..., 1],
-                              flags=0).astype(np.float64)
+                              flags=0, phase_yy=ph_yy).astype(np.float64)
 
     def write(self, out_dir, cellsize_deg, smooth_pix=0, ncpu=0):
         if self.data_rasertize_template is None:
@@ -343,11 +358,16 @@ class VoronoiScreen(Screen):
         from .streaming import PinnedPipeline
         dev, _ = self._device()
         ny, nx = self.data_rasertize_template.shape
-        n_f, n_a, D = self.vals_ph.shape[1:]
+        n_f, n_a, D = self.vals_ph.shape[1:4]
         per_slot = 16 * nx * ny
         row_bytes = n_f * n_a * per_slot
         rows = min(max(1, int(max_batch_bytes // row_bytes)), g_stop - g_start)
-        ph = self._upload(self.vals_ph[g_start:g_stop])
+        pyy = None
+        if self.pol_phases:
+            ph = self._upload(self.vals_ph[g_start:g_stop, ..., 0])
+            pyy = self._upload(self.vals_ph[g_start:g_stop, ..., 1])
+        else:
+            ph = self._upload(self.vals_ph[g_start:g_stop])
         axx = ayy = None
         if not self.phase_only:
             amp = np.asarray(self.vals_amp)[g_start:g_stop]
@@ -362,7 +382,8 @@ class VoronoiScreen(Screen):
                 self.eval_device(ph[s0:s1], out, smooth_pix,
                                  SF_EVAL_NAN_SCRUB | SF_EVAL_BIG_ENDIAN,
                                  amp_xx=None if axx is None else axx[s0:s1],
-                                 amp_yy=None if ayy is None else ayy[s0:s1])
+                                 amp_yy=None if ayy is None else ayy[s0:s1],
+                                 phase_yy=None if pyy is None else pyy[s0:s1])
                 pipe.submit(slot, (s1 - s0) * per_slot, writer)
         finally:
             pipe.close()
