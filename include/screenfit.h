@@ -243,6 +243,14 @@ int sf_device_cus(sf_ctx* ctx, int* n_cu);
 /* SF_OPT_FIT_WIDE_POOL_MAX: cap of the pool's number of entries (0 = default:
  * none beyond the byte cap); a small value forces the fallback above. */
 #define SF_OPT_FIT_WIDE_POOL_MAX 21
+/* SF_OPT_FIT_LANE = 0 / 1 (default 1): phase fits with 3..23 directions give
+ * the slots that start with every direction unflagged and one weight to a
+ * kernel that fits one slot per lane (64 consecutive slots per wavefront),
+ * and the pass kernel walks a list of the other slots instead of all of
+ * them.  A lane slot whose order walk moves, or with a phase that is not
+ * finite, goes back to the pass kernel.  Same results bit for bit; 0 (and
+ * SF_OPT_FIT_PACK = 0) runs every slot through the pass kernel. */
+#define SF_OPT_FIT_LANE 22
 #define SF_EVAL_KERNEL_AUTO 0
 #define SF_EVAL_KERNEL_TILE 1
 #define SF_EVAL_KERNEL_LDS4 2
@@ -378,6 +386,11 @@ int sf_kl_fit(sf_ctx* ctx, const double* phase, const float* weight, int T,
  * slots that took the general (tiny-weight) path.  (Wide-basis context:
  * see sf_set_basis_wide.) */
 int sf_get_fit_stats(sf_ctx* ctx, int* n_masks, int* n_general);
+
+/* Of the last sf_kl_fit (synchronises): the slots the lane-per-slot kernel
+ * took (SF_OPT_FIT_LANE) and how many of those it handed back to the pass
+ * kernel.  Both 0 where that kernel did not run. */
+int sf_get_fit_lane_stats(sf_ctx* ctx, int64_t* n_lane, int64_t* n_deferred);
 
 /* The subset bases the last sf_kl_fit decomposed (a test / inspection
  * hook; every call renumbers and rebuilds its pool): up to max_masks

@@ -150,6 +150,7 @@ int sf_destroy(sf_ctx* ctx) {
   hipFree(ctx->d_pos);
   hipFree(ctx->d_sigma);
   hipFree(ctx->d_class);
+  hipFree(ctx->d_list);
   hipFree(ctx->d_counters);
   hipFree(ctx->d_scratch);
   hipFree(ctx->d_wscratch);
@@ -224,6 +225,9 @@ int sf_set_option(sf_ctx* ctx, int option, int value) {
       return SF_OK;
     case SF_OPT_FIT_LEAN:
       ctx->fit_lean = value != 0;
+      return SF_OK;
+    case SF_OPT_FIT_LANE:
+      ctx->fit_lane = value != 0;
       return SF_OK;
     case SF_OPT_EVAL_KS_PAD:
       SF_REQUIRE(value >= 0 && value <= 3, SF_EINVAL,
@@ -533,6 +537,18 @@ int sf_get_fit_stats(sf_ctx* ctx, int* n_masks, int* n_general) {
   static_assert(sf::kCntIds == sf::kCntWideDecomp, "n_masks reads one slot");
   if (n_masks) *n_masks = c[sf::kCntIds];
   if (n_general) *n_general = c[sf::kCntSlow];
+  return SF_OK;
+}
+
+int sf_get_fit_lane_stats(sf_ctx* ctx, int64_t* n_lane, int64_t* n_deferred) {
+  SF_REQUIRE(ctx, SF_EINVAL, "sf_get_fit_lane_stats: NULL context");
+  int c[sf::kFitCounters] = {};
+  SF_HIP(hipSetDevice(ctx->device));
+  SF_HIP(hipStreamSynchronize(ctx->stream));
+  if (ctx->d_counters)
+    SF_HIP(hipMemcpy(c, ctx->d_counters, sizeof(c), hipMemcpyDeviceToHost));
+  if (n_lane) *n_lane = c[sf::kCntLane];
+  if (n_deferred) *n_deferred = c[sf::kCntLaneDeferred];
   return SF_OK;
 }
 

@@ -33,6 +33,7 @@
 #include <cmath>
 #include <cstdlib>
 
+#include "kl_fit_lane.h"
 #include "kl_fit_pool.h"
 #include "kl_fit_steps.h"
 #include "sf_internal.h"
@@ -56,7 +57,7 @@ __global__ __launch_bounds__(256) void kl_classify_kernel(
     int* __restrict__ pos, uint8_t* __restrict__ cls,
     int* __restrict__ counters,
     double* __restrict__ coef, double* __restrict__ resid,
-    float* __restrict__ w_out, int32_t* __restrict__ order_out) {
+    float* __restrict__ w_out, int32_t* __restrict__ order_out, int lane_fit) {
   constexpr int kPerWave = 64 / GW;
   const int l = lane();
   const int g = l / GW;   // slot group within the wave
@@ -93,7 +94,7 @@ __global__ __launch_bounds__(256) void kl_classify_kernel(
   }
   if (d != 0) return;
   if (skipped) {
-    cls[s] = 1;
+    cls[s] = kClassSkipped;
     order_out[s] = 0;
     pos[s] = -2;
     return;
@@ -101,7 +102,10 @@ __global__ __launch_bounds__(256) void kl_classify_kernel(
   order_out[s] = st_order[sg.a];
   if (tiny) atomicAdd(counters + kCntSlow, 1);
   else if (nonuniform) atomicAdd(counters + kCntNonUniform, 1);
-  cls[s] = tiny ? 2 : 0;
+  // lane_fit (kl_fit_lane.h): no flagged direction and one weight -> a lane
+  // of kl_fit_lane_kernel, which also lists the fast-class slots
+  const bool to_lane = lane_fit && !tiny && !nonuniform && mask == full_mask(D);
+  cls[s] = tiny ? kClassSlow : to_lane ? kClassLane : kClassFast;
   if (mask == full_mask(D)) pos[s] = -1;
   else if (mask == 0ull) pos[s] = -2;
   else pos[s] = table_insert(keys, cap, mask);
@@ -332,7 +336,7 @@ __global__ __launch_bounds__(256, SLOW ? 1 : SF_FIT_MINW) void kl_fit_pass_kerne
     const double* __restrict__ pool, int pool_cap, int* __restrict__ counters,
     int screen_type, double nsigma, int adjust_order, double* __restrict__ coef,
     double* __restrict__ resid, float* __restrict__ w_out,
-    int32_t* __restrict__ order_out) {
+    int32_t* __restrict__ order_out, const long long* __restrict__ list) {
 #pragma clang fp contract(off)
   extern __shared__ double smem[];
   const int ld = odd_ld(D);
@@ -376,8 +380,18 @@ __global__ __launch_bounds__(256, SLOW ? 1 : SF_FIT_MINW) void kl_fit_pass_kerne
   }
   const uint8_t want = SLOW ? 2 : 0;
 
-  for (int64_t s = (int64_t)blockIdx.x * nslots + wv; s < S;
-       s += (int64_t)gridDim.x * nslots) {
+  // list (kl_fit_lane.h): the fast-class slots of a fit whose other slots
+  // the lane kernel took, each with the first pass it is owed; its length is
+  // read here, the host never sees it.  Null: every slot.
+  const int64_t n_work = list ? (int64_t)counters[kCntList] : S;
+  for (int64_t i = (int64_t)blockIdx.x * nslots + wv; i < n_work;
+       i += (int64_t)gridDim.x * nslots) {
+    int64_t s = i;
+    if (list) {
+      const long long e = list[i];
+      if (list_first(e) > it) continue;
+      s = list_slot(e);
+    }
     // the slot's independent loads go out together (class, mask position,
     // phases, weights, state): checked one after another they were 4-5
     // serial global round trips per slot, the pass's main cost.  The rare
@@ -579,7 +593,8 @@ __global__ __launch_bounds__(256) void kl_block_flag_kernel(
 static int launch_pass(sf_ctx* ctx, bool slow, int it, const sf_fit_params* p,
                        const RefSpec& r, int64_t S, int F, int A,
                        const double* phase, double* coef, double* resid,
-                       float* w_out, int32_t* order_out, bool lean) {
+                       float* w_out, int32_t* order_out, bool lean,
+                       const long long* list) {
   const int D = ctx->D;
   const int spw = !slow && D <= 32 && ctx->fit_pack ? 2 : 1;
   lean = !slow && lean && ctx->fit_lean;
@@ -615,7 +630,7 @@ static int launch_pass(sf_ctx* ctx, bool slow, int it, const sf_fit_params* p,
                      ctx->d_pos, ctx->d_ids, ctx->d_keys, (int)ctx->table_cap,
                      ctx->d_pool, (int)ctx->pool_cap, ctx->d_counters,
                      p->screen_type, p->nsigma, p->adjust_order, coef, resid, w_out,
-                     order_out);
+                     order_out, list);
   SF_HIP(hipGetLastError());
   return SF_OK;
 }
@@ -689,6 +704,11 @@ int launch_fit(sf_ctx* ctx, const double* phase, const float* weight, int T,
                         ctx->stream));
   SF_HIP(hipMemsetAsync(ctx->d_ids, 0xff, ctx->table_cap * sizeof(int), ctx->stream));
   SF_HIP(hipMemsetAsync(ctx->d_counters, 0, kFitCounters * sizeof(int), ctx->stream));
+  // lane-per-slot kernel (kl_fit_lane.h): classify sets its slots aside, the
+  // lane kernel lists the others for the fast pass
+  const bool lane_fit = fit_lane_applies(ctx, p);
+  if (lane_fit) SF_TRY_RC(grow(&ctx->d_list, ctx->list_cap, (size_t)S));
+  long long* const list = lane_fit ? ctx->d_list : nullptr;
 
   {
     // lane groups of GW >= D lanes per slot, 4 waves per workgroup
@@ -702,7 +722,7 @@ int launch_fit(sf_ctx* ctx, const double* phase, const float* weight, int T,
     hipLaunchKernelGGL(classify, grid, dim3(256), 0, ctx->stream, weight, S, F, A, D,
                        ctx->d_st_order, ctx->d_skip, r.skip, ctx->d_keys, cap,
                        ctx->d_pos, ctx->d_class, ctx->d_counters, coef, resid, w_out,
-                       order_out);
+                       order_out, lane_fit ? 1 : 0);
     SF_HIP(hipGetLastError());
   }
 
@@ -710,11 +730,16 @@ int launch_fit(sf_ctx* ctx, const double* phase, const float* weight, int T,
   for (int it = 0; it < p->niter; ++it) {
     int n_slow = 0, n_nonuniform = 0;
     SF_TRY_RC(number_and_decompose(ctx, &n_slow, &n_nonuniform));
+    // every pass of the lane slots, where pass 0 starts: the masks of their
+    // pass-0 flags enter the table before the next numbering, as the pass
+    // kernel's do; the same launch lists the fast-class slots
+    if (it == 0 && lane_fit)
+      SF_TRY_RC(launch_fit_lane(ctx, p, r, S, A, phase, coef, resid, w_out, order_out));
     SF_TRY_RC(launch_pass(ctx, false, it, p, r, S, F, A, phase, coef, resid, w_out,
-                          order_out, n_nonuniform == 0));
+                          order_out, n_nonuniform == 0, list));
     if (n_slow > 0)
       SF_TRY_RC(launch_pass(ctx, true, it, p, r, S, F, A, phase, coef, resid, w_out,
-                            order_out, false));
+                            order_out, false, nullptr));
     if (block_flags && it + 1 < p->niter) {
       SF_TRY_RC(launch_block_sigma(ctx, T, F, A, phase, r, p->screen_type, resid,
                                  w_out));

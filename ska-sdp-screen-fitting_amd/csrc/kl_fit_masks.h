@@ -33,6 +33,25 @@ inline size_t next_pow2(size_t x, size_t floor) {
   return p;
 }
 
+constexpr unsigned long long kEmptyKey = 0ull;
+
+// Insert `key` (non-zero) into the open-addressing table; returns its slot
+// or -3 when the table is full.  Only ever inserts, never waits on other
+// threads (ids are assigned by a later kernel).
+__device__ inline int table_insert(unsigned long long* keys, int cap,
+                            unsigned long long key) {
+  int h = (int)(mix64(key) & (unsigned long long)(cap - 1));
+  for (int probe = 0; probe < cap; ++probe) {
+    // a plain load first: most slots share a few masks, whose entries are
+    // taken long before most inserts arrive -- no atomic on those
+    unsigned long long prev = keys[h];
+    if (prev == kEmptyKey) prev = atomicCAS(keys + h, kEmptyKey, key);
+    if (prev == kEmptyKey || prev == key) return h;
+    h = (h + 1) & (cap - 1);
+  }
+  return -3;
+}
+
 // Bound of a grid-stride loop of one thread per table entry i whose trips
 // are wave-uniform: a wave goes on while its first lane is inside the table,
 // so number_fresh below meets whole waves (entry i itself may lie beyond cap)

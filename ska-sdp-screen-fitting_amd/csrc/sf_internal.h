@@ -98,8 +98,12 @@ enum FitCounter {
   kCntNonUniform = 4,  // fast-class slots with unequal positive weights
   kCntMaxLevel = 5,    // deepest deletion level among this pass's new masks
   kCntWideMasks = 6,   // wide fit: distinct masks numbered
+  kCntLaneDeferred = 7,  // lane slots handed back to the pass kernel
+  kCntLane = 8,        // slots the lane kernel took (kl_fit_lane.hip) ...
+  kCntList = 9,        // ... entries of the pass kernel's work list: an
+                       // aligned pair, one 64-bit atomic adds to both
 };
-constexpr int kFitCounters = 8;
+constexpr int kFitCounters = 12;
 enum FitError {
   kErrLookupMiss = 1,      // a slot's mask has no pool id
   kErrTableFull = 2,       // the mask table took no further key
@@ -212,7 +216,9 @@ struct sf_ctx {
   size_t pool_status_cap = 0;
   int pool_D = 0;
   int* d_pos = nullptr;                  // [S] table slot of the current mask
-  uint8_t* d_class = nullptr;            // [S] 0 fast, 1 skipped, 2 slow
+  uint8_t* d_class = nullptr;            // [S] 0 fast, 1 skipped, 2 slow, 3 lane
+  long long* d_list = nullptr;           // [S] work list of the fast pass (kl_fit_lane.h)
+  size_t list_cap = 0;
   double* d_sigma = nullptr;             // [F][A] tec/amplitude block sigma
   size_t sigma_cap = 0;
   size_t slot_cap = 0;
@@ -249,6 +255,7 @@ struct sf_ctx {
   int tess_box = -1;            // SF_OPT_TESS_BOX (-1 auto, 0 wide-tile, 1 interior lookups)
   int fit_pack = 1;             // SF_OPT_FIT_PACK: 2 slots per wave for D <= 32
   int fit_lean = 1;             // SF_OPT_FIT_LEAN: lean pass when weights are uniform
+  int fit_lane = 1;             // SF_OPT_FIT_LANE: lane-per-slot kernel + work list
 };
 
 namespace sf {

@@ -47,6 +47,7 @@ SF_OPT_FIT_SUBSET_DELETION = 18
 SF_OPT_FIT_WIDE_CACHE = 19
 SF_OPT_FIT_WIDE_POOL_MB = 20
 SF_OPT_FIT_WIDE_POOL_MAX = 21
+SF_OPT_FIT_LANE = 22
 SF_EVAL_KERNEL_AUTO = 0
 SF_EVAL_KERNEL_TILE = 1
 SF_EVAL_KERNEL_LDS4 = 2
@@ -71,7 +72,7 @@ EVAL_KERNEL_NAMES = {SF_EVAL_KERNEL_TILE: "kl_eval_kernel",
 EXPORTED = (
     "sf_version", "sf_last_error", "sf_create", "sf_destroy", "sf_set_stream",
     "sf_synchronize", "sf_set_option", "sf_get_eval_kernel", "sf_get_eval_contraction", "sf_alloc", "sf_free", "sf_copy_h2d", "sf_copy_d2h",
-    "sf_set_basis", "sf_set_basis_wide", "sf_set_piercepoints", "sf_get_basis", "sf_kl_fit", "sf_get_fit_stats", "sf_get_fit_pool",
+    "sf_set_basis", "sf_set_basis_wide", "sf_set_piercepoints", "sf_get_basis", "sf_kl_fit", "sf_get_fit_stats", "sf_get_fit_lane_stats", "sf_get_fit_pool",
     "sf_get_fit_pool_wide",
     "sf_stream_create", "sf_stream_destroy", "sf_device_cus",
     "sf_set_grid", "sf_kl_eval", "sf_kl_eval_gain", "sf_kl_eval_sums",
@@ -153,6 +154,7 @@ def load_library(path=None):
             "sf_kl_fit": ([vp, vp, vp, c_int, c_int, c_int, ip,
                            ctypes.POINTER(FitParams), vp, vp, vp, vp], c_int),
             "sf_get_fit_stats": ([vp, ip, ip], c_int),
+            "sf_get_fit_lane_stats": ([vp, ctypes.POINTER(i64), ctypes.POINTER(i64)], c_int),
             "sf_get_fit_pool": ([vp, vp, vp, c_int, ip], c_int),
             "sf_get_fit_pool_wide": ([vp, vp, vp, c_int, ip], c_int),
             "sf_set_grid": ([vp, vp, c_int, vp, c_int], c_int),
@@ -359,6 +361,14 @@ class Context:
         _check(self.lib.sf_get_fit_stats(self.h, ctypes.byref(nm), ctypes.byref(ng)),
                "sf_get_fit_stats")
         return {"n_masks": nm.value, "n_general": ng.value}
+
+    def fit_lane_stats(self):
+        """Slots the lane-per-slot kernel took in the last fit and how many
+        of them it handed back to the pass kernel (sf_get_fit_lane_stats)."""
+        nl, nd = ctypes.c_int64(), ctypes.c_int64()
+        _check(self.lib.sf_get_fit_lane_stats(self.h, ctypes.byref(nl), ctypes.byref(nd)),
+               "sf_get_fit_lane_stats")
+        return {"n_lane": nl.value, "n_deferred": nd.value}
 
     def fit_pool(self):
         """The subset bases decomposed so far (sf_get_fit_pool), sorted by

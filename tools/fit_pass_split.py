@@ -62,4 +62,4 @@ for niter, adjust, dele in runs:
         e1.synchronize()
         ms.append(e0.elapsed_time(e1))
     print(f"{wl} S={T * F * A} niter={niter} adjust_order={adjust} deletion={dele}: "
-          f"{np.median(ms):.2f} ms  {ctx.fit_stats()}", flush=True)
+          f"{np.median(ms):.2f} ms  {ctx.fit_stats()} {ctx.fit_lane_stats()}", flush=True)
