@@ -39,47 +39,27 @@ int check_device(int device) {
   return SF_OK;
 }
 
+// A buffer of a geometry, a grid or a point set, bound anew at exactly its
+// size (the documented footprint): the previous one goes first.
 template <typename T>
-int dev_alloc(T** p, size_t count) {
-  if (*p) {
-    hipFree(*p);
-    *p = nullptr;
-  }
-  if (count == 0) return SF_OK;
-  if (hipMalloc(reinterpret_cast<void**>(p), count * sizeof(T)) != hipSuccess) {
-    *p = nullptr;
-    set_error("hipMalloc failed");
-    return SF_ENOMEM;
-  }
-  return SF_OK;
-}
-
-// the mask cache of the wide fit: slot keys, table, pool
-void free_wide_cache(sf_ctx* ctx) {
-  hipFree(ctx->d_wkeys);
-  hipFree(ctx->d_wslot);
-  hipFree(ctx->d_wtab);
-  hipFree(ctx->d_wtab_id);
-  hipFree(ctx->d_wpool_mask);
-  hipFree(ctx->d_wpool);
-  ctx->d_wkeys = nullptr;
-  ctx->d_wslot = nullptr;
-  ctx->d_wtab = nullptr;
-  ctx->d_wtab_id = nullptr;
-  ctx->d_wpool_mask = nullptr;
-  ctx->d_wpool = nullptr;
-  ctx->wslot_cap = ctx->wtab_cap = ctx->wpool_mask_cap = ctx->wpool_cap = 0;
-  ctx->wide_pool_n = 0;
+int rebind(sf::DevBuf<T>& b, size_t count) {
+  b.reset();
+  return b.reserve(count, "hipMalloc failed");
 }
 
 // A new geometry: the workspace of the wide fit (kl_fit_wide.hip) was sized
-// for the previous D, and its pool holds the previous geometry's bases.
+// for the previous D, and its mask cache (slot keys, table, pool) holds the
+// previous geometry's bases.
 void drop_wide(sf_ctx* ctx) {
   ctx->wide = 0;
-  hipFree(ctx->d_wide_ws);
-  ctx->d_wide_ws = nullptr;
-  ctx->wide_ws_cap = 0;
-  free_wide_cache(ctx);
+  ctx->d_wide_ws.reset();
+  ctx->d_wkeys.reset();
+  ctx->d_wslot.reset();
+  ctx->d_wtab.reset();
+  ctx->d_wtab_id.reset();
+  ctx->d_wpool_mask.reset();
+  ctx->d_wpool.reset();
+  ctx->wide_pool_n = 0;
 }
 
 // No geometry, no grid, no points, wide state dropped: the context while a
@@ -93,12 +73,6 @@ void drop_geometry(sf_ctx* ctx) {
   ctx->n_pix = 0;
   ctx->n_points = 0;
 }
-
-#define SF_TRY(x)              \
-  do {                         \
-    int rc_ = (x);             \
-    if (rc_ != SF_OK) return rc_; \
-  } while (0)
 
 }  // namespace
 
@@ -114,9 +88,8 @@ int sf_create(int device, sf_ctx** out) {
   SF_HIP(hipSetDevice(device));
   sf_ctx* ctx = new sf_ctx();
   ctx->device = device;
-  if (hipMalloc(reinterpret_cast<void**>(&ctx->d_trash), 1024) != hipSuccess) {
+  if (ctx->d_trash.reserve(256, "sf_create: hipMalloc failed") != SF_OK) {
     delete ctx;
-    set_error("sf_create: hipMalloc failed");
     return SF_ENOMEM;
   }
   *out = ctx;
@@ -126,40 +99,7 @@ int sf_create(int device, sf_ctx** out) {
 int sf_destroy(sf_ctx* ctx) {
   if (!ctx) return SF_OK;
   hipSetDevice(ctx->device);
-  hipFree(ctx->d_pp);
-  hipFree(ctx->d_c);
-  hipFree(ctx->d_pinv);
-  hipFree(ctx->d_u);
-  hipFree(ctx->d_eig);
-  hipFree(ctx->d_wide_ws);
-  free_wide_cache(ctx);
-  hipFree(ctx->d_cfrag);
-  hipFree(ctx->d_pxy);
-  hipFree(ctx->d_pfrag);
-  hipFree(ctx->d_cdig);
-  hipFree(ctx->d_kdig);
-  hipFree(ctx->d_kflag);
   if (ctx->kdig_read) (void)hipEventDestroy(ctx->kdig_read);
-  hipFree(ctx->d_skip);
-  hipFree(ctx->d_st_order);
-  hipFree(ctx->d_keys);
-  hipFree(ctx->d_ids);
-  hipFree(ctx->d_pool_mask);
-  hipFree(ctx->d_pool);
-  hipFree(ctx->d_pool_status);
-  hipFree(ctx->d_pos);
-  hipFree(ctx->d_sigma);
-  hipFree(ctx->d_class);
-  hipFree(ctx->d_list);
-  hipFree(ctx->d_counters);
-  hipFree(ctx->d_scratch);
-  hipFree(ctx->d_wscratch);
-  hipFree(ctx->d_oscratch);
-  hipFree(ctx->d_gw);
-  hipFree(ctx->d_smooth);
-  hipFree(ctx->d_tess_tab);
-  hipFree(ctx->d_tec_ch);
-  hipFree(ctx->d_trash);
   delete ctx;
   return SF_OK;
 }
@@ -387,11 +327,11 @@ int sf_set_basis(sf_ctx* ctx, const double* pp, int D, double r0,
   SF_HIP(hipSetDevice(ctx->device));
   SF_HIP(hipStreamSynchronize(ctx->stream));
   drop_geometry(ctx);  // until the new basis is complete
-  SF_TRY(dev_alloc(&ctx->d_pp, (size_t)3 * D));
-  SF_TRY(dev_alloc(&ctx->d_c, (size_t)D * D));
-  SF_TRY(dev_alloc(&ctx->d_pinv, (size_t)D * D));
-  SF_TRY(dev_alloc(&ctx->d_u, (size_t)D * D));
-  SF_TRY(dev_alloc(&ctx->d_eig, (size_t)64));
+  SF_TRY(rebind(ctx->d_pp, (size_t)3 * D));
+  SF_TRY(rebind(ctx->d_c, (size_t)D * D));
+  SF_TRY(rebind(ctx->d_pinv, (size_t)D * D));
+  SF_TRY(rebind(ctx->d_u, (size_t)D * D));
+  SF_TRY(rebind(ctx->d_eig, (size_t)64));
   SF_HIP(hipMemcpy(ctx->d_pp, pp, sizeof(double) * 3 * D,
                    hipMemcpyHostToDevice));
   for (int i = 0; i < 3 * D; ++i) ctx->h_pp[i] = pp[i];
@@ -420,7 +360,7 @@ int sf_set_piercepoints(sf_ctx* ctx, const double* pp, int D, double r0,
   // as sf_set_basis; the eigen-basis buffers of an earlier sf_set_basis are
   // not this D's
   drop_geometry(ctx);
-  SF_TRY(dev_alloc(&ctx->d_pp, (size_t)3 * D));
+  SF_TRY(rebind(ctx->d_pp, (size_t)3 * D));
   SF_HIP(hipMemcpy(ctx->d_pp, pp, sizeof(double) * 3 * D,
                    hipMemcpyHostToDevice));
   for (int i = 0; i < 3 * D; ++i) ctx->h_pp[i] = pp[i];
@@ -443,10 +383,10 @@ int sf_set_basis_wide(sf_ctx* ctx, const double* pp, int D, double r0,
   // ... then C, pinv(C), U and the eigenvalues; until they are complete the
   // context has no geometry at all
   drop_geometry(ctx);
-  SF_TRY(dev_alloc(&ctx->d_c, (size_t)D * D));
-  SF_TRY(dev_alloc(&ctx->d_pinv, (size_t)D * D));
-  SF_TRY(dev_alloc(&ctx->d_u, (size_t)D * D));
-  SF_TRY(dev_alloc(&ctx->d_eig, (size_t)SF_MAX_FIT_DIR));
+  SF_TRY(rebind(ctx->d_c, (size_t)D * D));
+  SF_TRY(rebind(ctx->d_pinv, (size_t)D * D));
+  SF_TRY(rebind(ctx->d_u, (size_t)D * D));
+  SF_TRY(rebind(ctx->d_eig, (size_t)SF_MAX_FIT_DIR));
   SF_HIP(hipMemset(ctx->d_eig, 0, SF_MAX_FIT_DIR * sizeof(double)));
   ctx->D = D;
   int rc = sf::launch_basis_wide(ctx);
@@ -512,14 +452,8 @@ int sf_kl_fit(sf_ctx* ctx, const double* phase, const float* weight, int T,
   for (int a = 0; a < A; ++a)
     SF_REQUIRE(st_order[a] >= 0, SF_EINVAL, "sf_kl_fit: negative order");
   SF_HIP(hipSetDevice(ctx->device));
-  if (ctx->skip_cap < (size_t)F * A) {
-    SF_TRY(dev_alloc(&ctx->d_skip, (size_t)F * A));
-    ctx->skip_cap = (size_t)F * A;
-  }
-  if (ctx->st_order_cap < (size_t)A) {
-    SF_TRY(dev_alloc(&ctx->d_st_order, (size_t)A));
-    ctx->st_order_cap = (size_t)A;
-  }
+  SF_TRY(ctx->d_skip.reserve((size_t)F * A, "hipMalloc failed"));
+  SF_TRY(ctx->d_st_order.reserve((size_t)A, "hipMalloc failed"));
   SF_HIP(hipMemcpyAsync(ctx->d_st_order, st_order, sizeof(int) * A,
                         hipMemcpyHostToDevice, ctx->stream));
   return sf::launch_fit(ctx, phase, weight, T, F, A, p, coef, resid, w_out,
@@ -566,7 +500,7 @@ int sf_get_fit_pool(sf_ctx* ctx, uint64_t* masks_host, double* entries_host,
   if (ctx->d_counters)
     SF_HIP(hipMemcpy(&c0, ctx->d_counters + sf::kCntIds, sizeof(int),
                      hipMemcpyDeviceToHost));
-  const int n = ctx->pool_D == ctx->D && (size_t)c0 <= ctx->pool_cap ? c0 : 0;
+  const int n = ctx->pool_D == ctx->D && (size_t)c0 <= ctx->d_pool_mask.size() ? c0 : 0;
   *n_masks = n;
   const int k = n < max_masks ? n : max_masks;
   if (k > 0) {
@@ -617,15 +551,12 @@ int sf_set_grid(sf_ctx* ctx, const double* x, int nx, const double* y,
   ctx->ksteps = (ctx->D + 3) / 4;
   const size_t n = (size_t)ctx->n_pix_blocks * sf::kEvalWaves * ctx->ksteps *
                    sf::kTiles * 64;
-  SF_TRY(dev_alloc(&ctx->d_cfrag, n));
-  double* dx = nullptr;
-  double* dy = nullptr;
-  SF_TRY(dev_alloc(&dx, (size_t)nx));
-  int rc = dev_alloc(&dy, (size_t)ny);
-  if (rc != SF_OK) {
-    hipFree(dx);
-    return rc;
-  }
+  SF_TRY(rebind(ctx->d_cfrag, n));
+  sf::DevBuf<double> dx, dy;  // (freed after the synchronise below)
+  sf::DevBuf<int> dbad;
+  SF_TRY(dx.reserve((size_t)nx, "hipMalloc failed"));
+  SF_TRY(dy.reserve((size_t)ny, "hipMalloc failed"));
+  int rc = SF_OK;
   if (hipMemcpyAsync(dx, x, sizeof(double) * nx, hipMemcpyHostToDevice,
                      ctx->stream) != hipSuccess ||
       hipMemcpyAsync(dy, y, sizeof(double) * ny, hipMemcpyHostToDevice,
@@ -663,14 +594,13 @@ int sf_set_grid(sf_ctx* ctx, const double* x, int nx, const double* y,
   // balanced base-256 digits (|.| < 2^46.99); 2^46.9 leaves the margin, and
   // kl_cdig_kernel reports any value that still does not fit
   ctx->dig_ok = 0;
-  int* dbad = nullptr;
   if (rc == SF_OK && ctx->ksteps >= 12 && ctx->ksteps <= sf::kEvalMaxKS &&
       std::isfinite(cmax) &&
       cmax * 68719476736.0 < std::ldexp(1.0, 46) * 1.86) {
     // (no memory for the digits: the fp64 contraction serves, not an error)
-    if (dev_alloc(&ctx->d_cdig, (size_t)ctx->n_pix_blocks * sf::kEvalWaves *
-                                    sf::kDigits * sf::kTiles * 64 * 16) == SF_OK &&
-        dev_alloc(&dbad, 1) == SF_OK &&
+    if (rebind(ctx->d_cdig, (size_t)ctx->n_pix_blocks * sf::kEvalWaves * sf::kDigits *
+                                sf::kTiles * 64 * 16) == SF_OK &&
+        dbad.reserve(1, "hipMalloc failed") == SF_OK &&
         hipMemsetAsync(dbad, 0, sizeof(int), ctx->stream) == hipSuccess) {
       rc = sf::launch_cdig(ctx, dx, dy, dbad);
       if (rc == SF_OK) ctx->dig_ok = 1;
@@ -685,9 +615,6 @@ int sf_set_grid(sf_ctx* ctx, const double* x, int nx, const double* y,
     if (hipMemcpy(&bad, dbad, sizeof(int), hipMemcpyDeviceToHost) != hipSuccess || bad)
       ctx->dig_ok = 0;
   }
-  (void)hipFree(dbad);
-  (void)hipFree(dx);
-  (void)hipFree(dy);
   if (rc == SF_OK) {
     // per lane (a quarter of a slot's directions): 2^17 / 4 turns
     ctx->rev_thr = cmax > 0.0 && std::isfinite(cmax) ? 32768.0 / cmax : 0.0;
@@ -755,8 +682,8 @@ int sf_set_points(sf_ctx* ctx, const double* xy, int P) {
   ctx->n_points = 0;  // no usable points until the basis is built
   if (ctx->pt_cus == 0) SF_TRY(sf_device_cus(ctx, &ctx->pt_cus));
   const int tiles = sf::points_tiles(P), ks_pad = sf::points_ks_pad(ctx->D);
-  SF_TRY(dev_alloc(&ctx->d_pxy, (size_t)2 * P));
-  SF_TRY(dev_alloc(&ctx->d_pfrag, (size_t)tiles * ks_pad * 64));
+  SF_TRY(rebind(ctx->d_pxy, (size_t)2 * P));
+  SF_TRY(rebind(ctx->d_pfrag, (size_t)tiles * ks_pad * 64));
   SF_HIP(hipMemcpy(ctx->d_pxy, xy, sizeof(double) * 2 * P, hipMemcpyHostToDevice));
   ctx->pt_tiles = tiles;
   ctx->pt_ks_pad = ks_pad;
@@ -876,20 +803,14 @@ int sf_set_tec_freqs(sf_ctx* ctx, const double* rad_per_tecu, const int* tec_ind
   // queued evaluations may still read the previous lists
   SF_HIP(hipStreamSynchronize(ctx->stream));
   // the new buffer first: a failure keeps the previous binding
-  double* d = nullptr;
-  const size_t bytes = (size_t)F * (sizeof(double) + sizeof(int));
-  if (hipMalloc(reinterpret_cast<void**>(&d), bytes) != hipSuccess) {
-    set_error("sf_set_tec_freqs: hipMalloc failed");
-    return SF_ENOMEM;
-  }
+  sf::DevBuf<double> d;  // F doubles, then F ints
+  SF_TRY(d.reserve((size_t)F + (F + 1) / 2, "sf_set_tec_freqs: hipMalloc failed"));
   if (hipMemcpy(d, k.data(), F * sizeof(double), hipMemcpyHostToDevice) != hipSuccess ||
       hipMemcpy(d + F, ch.data(), F * sizeof(int), hipMemcpyHostToDevice) != hipSuccess) {
-    (void)hipFree(d);
     set_error("sf_set_tec_freqs: copy of the channel lists failed");
     return SF_EIO;
   }
-  (void)hipFree(ctx->d_tec_ch);
-  ctx->d_tec_ch = d;
+  ctx->d_tec_ch.swap(d);
   ctx->tec_F = F;
   ctx->tec_F_tec = F_tec;
   ctx->tec_used.swap(used);
@@ -945,18 +866,7 @@ static int upload_gaussian(sf_ctx* ctx, double sigma, int* R_out) {
   // until the copy below has landed d_gw holds no sigma's weights: a failure
   // on the way must not leave the cache naming the old sigma
   ctx->gw_sigma = -1.0;
-  if (ctx->gw_cap < w.size()) {
-    if (ctx->d_gw) (void)hipFree(ctx->d_gw);
-    ctx->d_gw = nullptr;
-    ctx->gw_cap = 0;
-    const size_t cap = w.size() < 64 ? 64 : w.size();
-    if (hipMalloc(reinterpret_cast<void**>(&ctx->d_gw), cap * sizeof(double)) !=
-        hipSuccess) {
-      set_error("hipMalloc failed");
-      return SF_ENOMEM;
-    }
-    ctx->gw_cap = cap;
-  }
+  SF_TRY(ctx->d_gw.reserve(w.size() < 64 ? 64 : w.size(), "hipMalloc failed"));
   SF_HIP(hipMemcpyAsync(ctx->d_gw, w.data(), w.size() * sizeof(double),
                         hipMemcpyHostToDevice, ctx->stream));
   SF_HIP(hipStreamSynchronize(ctx->stream));

@@ -125,7 +125,7 @@ int launch_cdig(sf_ctx* ctx, const double* d_x, const double* d_y, int* d_bad) {
   const int64_t blocks = (n + 255) / 256;
   hipLaunchKernelGGL(kl_cdig_kernel, dim3((unsigned)blocks), dim3(256), 0,
                      ctx->stream, ctx->d_pp, ctx->D, ctx->r0, ctx->beta, d_x,
-                     ctx->nx, d_y, ctx->ny, n, reinterpret_cast<v4i*>(ctx->d_cdig),
+                     ctx->nx, d_y, ctx->ny, n, reinterpret_cast<v4i*>(ctx->d_cdig.get()),
                      d_bad);
   SF_HIP(hipGetLastError());
   return SF_OK;

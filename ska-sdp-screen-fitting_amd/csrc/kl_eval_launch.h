@@ -96,20 +96,9 @@ inline int64_t eval_launch_slots(const sf_ctx* ctx, int64_t n_pb, int groups,
 constexpr int64_t kDigChunk = (int64_t)1 << 20;
 
 inline int ensure_kdig(sf_ctx* ctx, int64_t slots) {
-  if (ctx->kdig_slots >= slots) return SF_OK;
   // (hipFree waits for the device, so no reader of the old buffers remains)
-  (void)hipFree(ctx->d_kdig);
-  (void)hipFree(ctx->d_kflag);
-  ctx->d_kdig = nullptr;
-  ctx->d_kflag = nullptr;
-  ctx->kdig_slots = 0;
-  if (hipMalloc(reinterpret_cast<void**>(&ctx->d_kdig), (size_t)slots * kDigits * 64) != hipSuccess ||
-      hipMalloc(reinterpret_cast<void**>(&ctx->d_kflag), (size_t)slots) != hipSuccess) {
-    set_error("sf_kl_eval: hipMalloc of the integer-contraction digits failed");
-    return SF_ENOMEM;
-  }
-  ctx->kdig_slots = slots;
-  return SF_OK;
+  return reserve_pair(ctx->d_kdig, (size_t)slots * kDigits * 64, ctx->d_kflag, (size_t)slots,
+                      "sf_kl_eval: hipMalloc of the integer-contraction digits failed");
 }
 
 // Prepass of one integer-contraction launch: the digit rows and flags of S
@@ -139,7 +128,7 @@ template <bool IC>
 DigArgs dig_args(const sf_ctx* ctx) {
   DigArgs dg{};
   if (IC) {
-    dg.cdig = reinterpret_cast<const v4i*>(ctx->d_cdig);
+    dg.cdig = reinterpret_cast<const v4i*>(ctx->d_cdig.get());
     dg.kdig = ctx->d_kdig;
     dg.kflag = ctx->d_kflag;
   }
@@ -267,13 +256,13 @@ inline EvalStep eval_step(const EvalCall& c, const EvalPlan& p, int64_t b, int64
 template <class F>
 int eval_split(const EvalCall& c, const EvalPlan& p, F&& launch) {
   sf_ctx* ctx = c.ctx;
-  if (p.ic) SF_TRY_RC(ensure_kdig(ctx, c.S_all < p.per ? c.S_all : p.per));
+  if (p.ic) SF_TRY(ensure_kdig(ctx, c.S_all < p.per ? c.S_all : p.per));
   for (int64_t b = 0; b < c.S_all; b += p.per) {
     const EvalStep s = eval_step(c, p, b, c.S_all - b < p.per ? c.S_all - b : p.per);
-    if (p.ic) SF_TRY_RC(run_kdig(ctx, s.cb, s.S));
+    if (p.ic) SF_TRY(run_kdig(ctx, s.cb, s.S));
     launch(s);
     SF_HIP(hipGetLastError());
-    if (p.ic) SF_TRY_RC(kdig_done(ctx));
+    if (p.ic) SF_TRY(kdig_done(ctx));
   }
   return SF_OK;
 }

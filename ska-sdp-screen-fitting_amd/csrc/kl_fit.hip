@@ -315,7 +315,7 @@ int launch_fit_general(sf_ctx* ctx, const double* phase, const float* weight,
   int64_t blocks = ((int64_t)T * F * A + nw - 1) / nw;
   if (blocks > 4096) blocks = 4096;
   if (blocks < 1) blocks = 1;
-  SF_TRY_RC(allow_lds(kl_fit_general_kernel, shm));
+  SF_TRY(allow_lds(kl_fit_general_kernel, shm));
   hipLaunchKernelGGL(kl_fit_general_kernel, dim3((unsigned)blocks),
                      dim3(64 * nw), shm, ctx->stream, phase, weight, T, F, A, D,
                      ctx->d_st_order, ctx->d_skip, r.refph, ctx->d_c, ctx->d_u, ctx->d_eig, p->screen_type, p->niter,

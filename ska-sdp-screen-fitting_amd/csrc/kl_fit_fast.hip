@@ -621,14 +621,14 @@ static int launch_pass(sf_ctx* ctx, bool slow, int it, const sf_fit_params* p,
     }
   }
   const size_t shm = shared + (size_t)nw * spw * slot;
-  SF_TRY_RC(allow_lds(kernel, shm));
+  SF_TRY(allow_lds(kernel, shm));
   int64_t blocks = (S + nw * spw - 1) / (nw * spw);
   if (blocks > 16384) blocks = 16384;
   hipLaunchKernelGGL(kernel, dim3((unsigned)blocks), dim3(64 * nw), shm,
                      ctx->stream, it, p->niter, S, F, A, D, phase, r.refph, r.sub,
                      ctx->d_u, ctx->d_c, ctx->d_eig, ctx->d_st_order, ctx->d_class,
-                     ctx->d_pos, ctx->d_ids, ctx->d_keys, (int)ctx->table_cap,
-                     ctx->d_pool, (int)ctx->pool_cap, ctx->d_counters,
+                     ctx->d_pos, ctx->d_ids, ctx->d_keys, (int)ctx->d_keys.size(),
+                     ctx->d_pool, (int)ctx->d_pool_mask.size(), ctx->d_counters,
                      p->screen_type, p->nsigma, p->adjust_order, coef, resid, w_out,
                      order_out, list);
   SF_HIP(hipGetLastError());
@@ -653,19 +653,19 @@ int fit_buffers(sf_ctx* ctx, int64_t S, int F, int A, double** resid,
                 float** w_out, int32_t** order_out) {
   const size_t n = (size_t)S * ctx->D;
   if (!*resid) {
-    SF_TRY_RC(grow(&ctx->d_scratch, ctx->scratch_cap, n));
+    SF_TRY(ctx->d_scratch.reserve(n, kFitAlloc));
     *resid = ctx->d_scratch;
   }
   if (!*w_out) {
-    SF_TRY_RC(grow(&ctx->d_wscratch, ctx->wscratch_cap, n));
+    SF_TRY(ctx->d_wscratch.reserve(n, kFitAlloc));
     *w_out = ctx->d_wscratch;
   }
   if (!*order_out) {
-    SF_TRY_RC(grow(&ctx->d_oscratch, ctx->oscratch_cap, (size_t)S));
+    SF_TRY(ctx->d_oscratch.reserve((size_t)S, kFitAlloc));
     *order_out = ctx->d_oscratch;
   }
-  SF_TRY_RC(grow(&ctx->d_sigma, ctx->sigma_cap, (size_t)F * A));
-  SF_TRY_RC(grow(&ctx->d_counters, ctx->counters_cap, (size_t)kFitCounters));
+  SF_TRY(ctx->d_sigma.reserve((size_t)F * A, kFitAlloc));
+  SF_TRY(ctx->d_counters.reserve((size_t)kFitCounters, kFitAlloc));
   return SF_OK;
 }
 
@@ -678,7 +678,7 @@ int launch_fit(sf_ctx* ctx, const double* phase, const float* weight, int T,
   const int D = ctx->D;
   const int64_t S = (int64_t)T * F * A;
   const RefSpec r = ref_spec(p, A);
-  SF_TRY_RC(launch_skip(ctx, phase, weight, T, F, A, r));
+  SF_TRY(launch_skip(ctx, phase, weight, T, F, A, r));
 
   static const char* env = std::getenv("SCREENFIT_FIT");
   if (ctx->force_general || (env && env[0] == 'g')) {
@@ -690,24 +690,21 @@ int launch_fit(sf_ctx* ctx, const double* phase, const float* weight, int T,
     return launch_fit_general(ctx, phase, weight, T, F, A, p, r, coef, resid,
                               w_out, order_out);
   }
-  SF_TRY_RC(fit_buffers(ctx, S, F, A, &resid, &w_out, &order_out));
-  if (ctx->slot_cap < (size_t)S)
-    SF_TRY_RC(replace_pair(ctx->slot_cap, (size_t)S, &ctx->d_pos, (size_t)S,
-                           &ctx->d_class, (size_t)S));
+  SF_TRY(fit_buffers(ctx, S, F, A, &resid, &w_out, &order_out));
+  SF_TRY(reserve_pair(ctx->d_pos, (size_t)S, ctx->d_class, (size_t)S, kFitAlloc));
   // every pass inserts at most one mask per slot
   const size_t tcap = next_pow2((size_t)(2 * p->niter + 2) * (size_t)S + 64, 1);
-  if (ctx->table_cap < tcap)
-    SF_TRY_RC(replace_pair(ctx->table_cap, tcap, &ctx->d_keys, tcap, &ctx->d_ids, tcap));
-  SF_TRY_RC(ensure_pool(ctx, 1024));
-  const int cap = (int)ctx->table_cap;
-  SF_HIP(hipMemsetAsync(ctx->d_keys, 0, ctx->table_cap * sizeof(unsigned long long),
-                        ctx->stream));
-  SF_HIP(hipMemsetAsync(ctx->d_ids, 0xff, ctx->table_cap * sizeof(int), ctx->stream));
+  SF_TRY(reserve_pair(ctx->d_keys, tcap, ctx->d_ids, tcap, kFitAlloc));
+  SF_TRY(ensure_pool(ctx, 1024));
+  // (the table may be a larger power of two than tcap: an earlier call's)
+  const int cap = (int)ctx->d_keys.size();
+  SF_HIP(hipMemsetAsync(ctx->d_keys, 0, cap * sizeof(unsigned long long), ctx->stream));
+  SF_HIP(hipMemsetAsync(ctx->d_ids, 0xff, cap * sizeof(int), ctx->stream));
   SF_HIP(hipMemsetAsync(ctx->d_counters, 0, kFitCounters * sizeof(int), ctx->stream));
   // lane-per-slot kernel (kl_fit_lane.h): classify sets its slots aside, the
   // lane kernel lists the others for the fast pass
   const bool lane_fit = fit_lane_applies(ctx, p);
-  if (lane_fit) SF_TRY_RC(grow(&ctx->d_list, ctx->list_cap, (size_t)S));
+  if (lane_fit) SF_TRY(ctx->d_list.reserve((size_t)S, kFitAlloc));
   long long* const list = lane_fit ? ctx->d_list : nullptr;
 
   {
@@ -729,19 +726,19 @@ int launch_fit(sf_ctx* ctx, const double* phase, const float* weight, int T,
   const bool block_flags = p->screen_type != SF_SCREEN_PHASE;
   for (int it = 0; it < p->niter; ++it) {
     int n_slow = 0, n_nonuniform = 0;
-    SF_TRY_RC(number_and_decompose(ctx, &n_slow, &n_nonuniform));
+    SF_TRY(number_and_decompose(ctx, &n_slow, &n_nonuniform));
     // every pass of the lane slots, where pass 0 starts: the masks of their
     // pass-0 flags enter the table before the next numbering, as the pass
     // kernel's do; the same launch lists the fast-class slots
     if (it == 0 && lane_fit)
-      SF_TRY_RC(launch_fit_lane(ctx, p, r, S, A, phase, coef, resid, w_out, order_out));
-    SF_TRY_RC(launch_pass(ctx, false, it, p, r, S, F, A, phase, coef, resid, w_out,
+      SF_TRY(launch_fit_lane(ctx, p, r, S, A, phase, coef, resid, w_out, order_out));
+    SF_TRY(launch_pass(ctx, false, it, p, r, S, F, A, phase, coef, resid, w_out,
                           order_out, n_nonuniform == 0, list));
     if (n_slow > 0)
-      SF_TRY_RC(launch_pass(ctx, true, it, p, r, S, F, A, phase, coef, resid, w_out,
+      SF_TRY(launch_pass(ctx, true, it, p, r, S, F, A, phase, coef, resid, w_out,
                             order_out, false, nullptr));
     if (block_flags && it + 1 < p->niter) {
-      SF_TRY_RC(launch_block_sigma(ctx, T, F, A, phase, r, p->screen_type, resid,
+      SF_TRY(launch_block_sigma(ctx, T, F, A, phase, r, p->screen_type, resid,
                                  w_out));
       hipLaunchKernelGGL(kl_block_flag_kernel, dim3((unsigned)((S + 255) / 256)),
                          dim3(256), 0, ctx->stream, S, F, A, D, phase, r.refph,

@@ -388,7 +388,7 @@ static void launch_lane(sf_ctx* ctx, const sf_fit_params* p, const RefSpec& r,
   hipLaunchKernelGGL(kl_fit_lane_kernel<D>, dim3((unsigned)((S + 63) / 64)), dim3(64), 0,
                      ctx->stream, p->niter, S, A, phase, r.refph, r.sub, ctx->d_u,
                      ctx->d_eig, ctx->d_st_order, ctx->d_class, ctx->d_pos, ctx->d_keys,
-                     (int)ctx->table_cap, ctx->d_counters, ctx->d_list, p->nsigma,
+                     (int)ctx->d_keys.size(), ctx->d_counters, ctx->d_list, p->nsigma,
                      p->adjust_order, coef, resid, w_out, order_out);
 }
 

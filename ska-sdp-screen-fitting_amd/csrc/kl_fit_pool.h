@@ -454,24 +454,19 @@ __global__ __launch_bounds__(64) void kl_subset_secular_kernel(
   }
 }
 
+// The pool holds `need` entries or more: d_pool_mask.size() of them, 1024
+// doubled as often as it takes, the earlier entries kept.
 static int ensure_pool(sf_ctx* ctx, size_t need) {
   const size_t entry = (size_t)ctx->D * ctx->D + ctx->D;
   if (ctx->pool_D != ctx->D) {
-    if (ctx->d_pool) (void)hipFree(ctx->d_pool);
-    if (ctx->d_pool_mask) (void)hipFree(ctx->d_pool_mask);
-    ctx->d_pool = nullptr;
-    ctx->d_pool_mask = nullptr;
-    ctx->pool_cap = 0;
+    ctx->d_pool.reset();
+    ctx->d_pool_mask.reset();
     ctx->pool_D = ctx->D;
   }
-  if (ctx->pool_cap >= need) return SF_OK;
-  size_t cap = ctx->pool_cap ? ctx->pool_cap : 1024;
+  size_t cap = ctx->d_pool_mask.size() ? ctx->d_pool_mask.size() : 1024;
   while (cap < need) cap *= 2;
-  size_t pc = ctx->pool_cap * entry, mc = ctx->pool_cap;
-  SF_TRY_RC(grow(&ctx->d_pool, pc, cap * entry, true));
-  SF_TRY_RC(grow(&ctx->d_pool_mask, mc, cap, true));
-  ctx->pool_cap = cap;
-  return SF_OK;
+  SF_TRY(ctx->d_pool.reserve_keep(cap * entry, kFitAlloc));
+  return ctx->d_pool_mask.reserve_keep(cap, kFitAlloc);
 }
 
 // pool_mask[id] for ids assigned beyond a previous pool capacity
@@ -492,8 +487,8 @@ static int number_and_decompose(sf_ctx* ctx, int* n_slow, int* n_nonuniform) {
   SF_HIP(hipMemcpyAsync(ctx->d_counters + kCntPassStart, ctx->d_counters + kCntIds,
                         sizeof(int), hipMemcpyDeviceToDevice, ctx->stream));
   SF_HIP(hipMemsetAsync(ctx->d_counters + kCntMaxLevel, 0, sizeof(int), ctx->stream));
-  const int cap = (int)ctx->table_cap;
-  const int old_cap = (int)ctx->pool_cap;
+  const int cap = (int)ctx->d_keys.size();
+  const int old_cap = (int)ctx->d_pool_mask.size();
   hipLaunchKernelGGL(kl_assign_kernel, dim3(std::min((cap + 255) / 256, 8192)), dim3(256), 0,
                      ctx->stream, ctx->d_keys, cap, ctx->d_ids,
                      ctx->d_pool_mask, old_cap, ctx->d_counters, ctx->D);
@@ -505,7 +500,7 @@ static int number_and_decompose(sf_ctx* ctx, int* n_slow, int* n_nonuniform) {
   *n_slow = cnt[kCntSlow];
   *n_nonuniform = cnt[kCntNonUniform];
   if (cnt[kCntIds] > old_cap) {
-    SF_TRY_RC(ensure_pool(ctx, (size_t)cnt[kCntIds]));
+    SF_TRY(ensure_pool(ctx, (size_t)cnt[kCntIds]));
     hipLaunchKernelGGL(kl_fill_mask_kernel, dim3((cap + 255) / 256), dim3(256),
                        0, ctx->stream, ctx->d_keys, ctx->d_ids, cap,
                        ctx->d_pool_mask, old_cap);
@@ -519,13 +514,14 @@ static int number_and_decompose(sf_ctx* ctx, int* n_slow, int* n_nonuniform) {
     // (the status of every pool entry of the call is kept: a later pass's
     // masks take an earlier pass's entries as ancestors only if the chain
     // built them; the stream was synchronised above, so the copy is safe)
-    SF_TRY_RC(grow(&ctx->d_pool_status, ctx->pool_status_cap, ctx->pool_cap, true));
+    SF_TRY(ctx->d_pool_status.reserve_keep(ctx->d_pool_mask.size(),
+                                           kFitAlloc));
     SF_HIP(hipMemsetAsync(ctx->d_pool_status + cnt[kCntPassStart], 1, (size_t)n_new, ctx->stream));
     const int D = ctx->D;
     const int ldd = odd_ld(D);
     const size_t shm = (size_t)2 * D * ldd * sizeof(double) + 6 * 64 * sizeof(double) +
                        4 * 64 * sizeof(int);
-    SF_TRY_RC(allow_lds(kl_subset_secular_kernel, shm));
+    SF_TRY(allow_lds(kl_subset_secular_kernel, shm));
     const int blocks = n_new < 16384 ? n_new : 16384;
     // levels 1 .. (most flagged directions), each mask from its nearest
     // decomposed ancestor (option 3, and option 1 -- the default -- when the
@@ -542,7 +538,7 @@ static int number_and_decompose(sf_ctx* ctx, int* n_slow, int* n_nonuniform) {
     const int levels = anc ? cnt[kCntMaxLevel] : 0;
     for (int lv = levels > 0 ? 1 : 0; lv <= levels; ++lv) {
       hipLaunchKernelGGL(kl_subset_secular_kernel, dim3(blocks), dim3(64), shm, ctx->stream,
-                         ctx->d_u, ctx->d_eig, D, ctx->d_pool_mask, (int)ctx->pool_cap,
+                         ctx->d_u, ctx->d_eig, D, ctx->d_pool_mask, (int)ctx->d_pool_mask.size(),
                          ctx->d_counters, ctx->d_pool, ctx->d_pool_status, ctx->d_keys,
                          ctx->d_ids, cap, lv);
       SF_HIP(hipGetLastError());
@@ -560,9 +556,9 @@ static int number_and_decompose(sf_ctx* ctx, int* n_slow, int* n_nonuniform) {
     decltype(&kl_subset_eig_kernel<1>) const eig[4] = {
         kl_subset_eig_kernel<1>, kl_subset_eig_kernel<2>, kl_subset_eig_kernel<3>,
         kl_subset_eig_kernel<4>};
-    SF_TRY_RC(allow_lds(eig[nw - 1], shm));
+    SF_TRY(allow_lds(eig[nw - 1], shm));
     hipLaunchKernelGGL(eig[nw - 1], dim3(blocks), dim3(64 * nw), shm, ctx->stream,
-                       ctx->d_c, D, ctx->d_pool_mask, (int)ctx->pool_cap,
+                       ctx->d_c, D, ctx->d_pool_mask, (int)ctx->d_pool_mask.size(),
                        ctx->d_counters, ctx->d_pool, done);
     SF_HIP(hipGetLastError());
   }

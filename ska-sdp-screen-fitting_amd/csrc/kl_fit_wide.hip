@@ -553,18 +553,13 @@ int build_wide_pool(sf_ctx* ctx, const float* weight, int64_t S, int F, int A,
     max_entries = (size_t)ctx->wide_pool_max;
   if (max_entries > (size_t)S) max_entries = (size_t)S;
   if (max_entries == 0) return SF_OK;
-  if (ctx->wslot_cap < (size_t)S)
-    SF_TRY_RC(replace_pair(ctx->wslot_cap, (size_t)S, &ctx->d_wkeys, (size_t)2 * S,
-                           &ctx->d_wslot, (size_t)S));
+  SF_TRY(reserve_pair(ctx->d_wkeys, (size_t)2 * S, ctx->d_wslot, (size_t)S, kFitAlloc));
   // at most one insert per slot: the table stays half empty
   const size_t tcap = next_pow2((size_t)2 * S, 64);
-  if (ctx->wtab_cap < tcap)
-    SF_TRY_RC(replace_pair(ctx->wtab_cap, tcap, &ctx->d_wtab, tcap, &ctx->d_wtab_id,
-                           tcap));
-  SF_TRY_RC(grow(&ctx->d_wpool_mask, ctx->wpool_mask_cap, 2 * max_entries));
-  const int cap = (int)ctx->wtab_cap;
-  SF_HIP(hipMemsetAsync(ctx->d_wtab, 0, ctx->wtab_cap * sizeof(unsigned long long),
-                        ctx->stream));
+  SF_TRY(reserve_pair(ctx->d_wtab, tcap, ctx->d_wtab_id, tcap, kFitAlloc));
+  SF_TRY(ctx->d_wpool_mask.reserve(2 * max_entries, kFitAlloc));
+  const int cap = (int)ctx->d_wtab.size();
+  SF_HIP(hipMemsetAsync(ctx->d_wtab, 0, cap * sizeof(unsigned long long), ctx->stream));
   hipLaunchKernelGGL(kl_wide_keys_kernel, dim3((unsigned)((S + 3) / 4)), dim3(256),
                      0, ctx->stream, weight, S, F, A, D, ctx->d_skip, ref_skip,
                      ctx->d_wkeys);
@@ -585,7 +580,7 @@ int build_wide_pool(sf_ctx* ctx, const float* weight, int64_t S, int F, int A,
   SF_HIP(hipStreamSynchronize(ctx->stream));
   const int n = (size_t)n_masks < max_entries ? n_masks : (int)max_entries;
   if (n == 0) return SF_OK;
-  SF_TRY_RC(grow(&ctx->d_wpool, ctx->wpool_cap, (size_t)n * entry));
+  SF_TRY(ctx->d_wpool.reserve((size_t)n * entry, kFitAlloc));
   hipLaunchKernelGGL(kl_wide_slot_id_kernel, dim3((unsigned)((S + 255) / 256)),
                      dim3(256), 0, ctx->stream, S, ctx->d_wtab_id, n, ctx->d_wslot);
   SF_HIP(hipGetLastError());
@@ -593,7 +588,7 @@ int build_wide_pool(sf_ctx* ctx, const float* weight, int64_t S, int F, int A,
   const int v_lds = wide_lds_mats(D) >= 2;
   const size_t shm = sizeof(WideSmall) +
                      (size_t)(v_lds ? 2 : 1) * D * odd_ld(D) * sizeof(double);
-  SF_TRY_RC(allow_lds(kl_wide_subset_kernel, shm));
+  SF_TRY(allow_lds(kl_wide_subset_kernel, shm));
   const int grid = n_cu > 0 && n_cu < n ? n_cu : n;
   hipLaunchKernelGGL(kl_wide_subset_kernel, dim3((unsigned)grid),
                      dim3(kWideThreads), shm, ctx->stream, n, D, v_lds, ctx->d_c,
@@ -645,7 +640,7 @@ size_t wide_basis_ws_doubles(int D) { return (size_t)2 * D * odd_ld(D); }
 
 int launch_basis_wide(sf_ctx* ctx) {
   const int D = ctx->D;
-  SF_TRY_RC(grow(&ctx->d_wide_ws, ctx->wide_ws_cap, wide_basis_ws_doubles(D)));
+  SF_TRY(ctx->d_wide_ws.reserve(wide_basis_ws_doubles(D), kFitAlloc));
   hipLaunchKernelGGL(kl_basis_wide_kernel, dim3(1), dim3(kWideThreads), 0,
                      ctx->stream, ctx->d_pp, D, ctx->r0, ctx->beta, ctx->d_c,
                      ctx->d_pinv, ctx->d_u, ctx->d_eig, ctx->d_wide_ws);
@@ -663,7 +658,7 @@ int launch_fit_wide(sf_ctx* ctx, const double* phase, const float* weight,
                      ctx->stream, phase, weight, T, F, A, D, r.sub, r.refph,
                      ctx->d_skip);
   SF_HIP(hipGetLastError());
-  SF_TRY_RC(fit_buffers(ctx, S, F, A, &resid, &w_out, &order_out));
+  SF_TRY(fit_buffers(ctx, S, F, A, &resid, &w_out, &order_out));
   SF_HIP(hipMemsetAsync(ctx->d_counters, 0, kFitCounters * sizeof(int), ctx->stream));
 
   // persistent grid: one workgroup per CU (the kernel's registers and, from
@@ -678,13 +673,13 @@ int launch_fit_wide(sf_ctx* ctx, const double* phase, const float* weight,
   int64_t grid = n_cu > 0 ? n_cu : 1;
   if (grid > S) grid = S;
   const size_t ws = (size_t)grid * (size_t)(3 - nl) * mat;
-  if (ws > 0) SF_TRY_RC(grow(&ctx->d_wide_ws, ctx->wide_ws_cap, ws));
-  SF_TRY_RC(allow_lds(kl_fit_wide_kernel, shm));
+  SF_TRY(ctx->d_wide_ws.reserve(ws, kFitAlloc));
+  SF_TRY(allow_lds(kl_fit_wide_kernel, shm));
 
   WidePool pool = {};
   ctx->wide_pool_n = 0;
   if (ctx->wide_cache)
-    SF_TRY_RC(build_wide_pool(ctx, weight, S, F, A, r.skip, n_cu, &pool));
+    SF_TRY(build_wide_pool(ctx, weight, S, F, A, r.skip, n_cu, &pool));
 
   {
     const int64_t n = S * D;
@@ -705,7 +700,7 @@ int launch_fit_wide(sf_ctx* ctx, const double* phase, const float* weight,
                        w_out, order_out);
     SF_HIP(hipGetLastError());
     if (block_flags && it + 1 < p->niter) {
-      SF_TRY_RC(launch_block_sigma(ctx, T, F, A, phase, r, p->screen_type,
+      SF_TRY(launch_block_sigma(ctx, T, F, A, phase, r, p->screen_type,
                                    resid, w_out));
       const int64_t n = S * D;
       hipLaunchKernelGGL(kl_wide_block_flag_kernel,

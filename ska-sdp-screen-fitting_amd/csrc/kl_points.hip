@@ -200,7 +200,7 @@ int launch_points_one(sf_ctx* ctx, const double* coef, const double* cxx,
                       const double* cyy, int64_t S, void* out, unsigned flags) {
   const size_t basis = (size_t)ctx->pt_tiles * ctx->pt_ks_pad * 64 * sizeof(double);
   const size_t shm = (LDSB ? basis : 0) + PtOut<MODE>::kStageBytes;
-  SF_TRY_RC(allow_lds(kl_eval_points_kernel<MODE, FAST, LDSB>, shm));
+  SF_TRY(allow_lds(kl_eval_points_kernel<MODE, FAST, LDSB>, shm));
   // persistent workgroups (each loads the basis once): as many as the LDS and
   // the 2048 threads of a CU hold
   const int64_t n_items = (S + 16 * kPtWaves - 1) / (16 * kPtWaves);

@@ -5,6 +5,7 @@
 
 #include <cstdint>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "screenfit.h"
@@ -31,51 +32,86 @@ void set_error(const std::string& msg);
     }                               \
   } while (0)
 
-#define SF_TRY_RC(x)               \
+#define SF_TRY(x)                  \
   do {                             \
     int rc_ = (x);                 \
     if (rc_ != SF_OK) return rc_;  \
   } while (0)
 
-// Device buffer of at least `need` elements (callers synchronise the
-// context's stream before growing, so queued kernels no longer write the old
-// buffer); keep = copy the old contents over.
+// Device memory that a context (or a call) owns: the pointer and its size in
+// elements, never one without the other.  Reads as a plain T* wherever a
+// kernel argument, a copy or a test for "allocated" wants one.  hipFree waits
+// for the device, so no queued kernel still uses a buffer that is let go.
 template <typename T>
-int grow(T** p, size_t& cap, size_t need, bool keep = false) {
-  if (*p && cap >= need) return SF_OK;
-  T* q = nullptr;
-  if (hipMalloc(reinterpret_cast<void**>(&q), need * sizeof(T)) != hipSuccess) {
-    set_error("hipMalloc failed (fit scratch)");
-    return SF_ENOMEM;
+class DevBuf {
+ public:
+  DevBuf() = default;
+  DevBuf(const DevBuf&) = delete;
+  DevBuf& operator=(const DevBuf&) = delete;
+  ~DevBuf() { reset(); }
+
+  operator T*() const { return p_; }
+  T* get() const { return p_; }
+  size_t size() const { return n_; }
+
+  void reset() {
+    if (p_) (void)hipFree(p_);
+    p_ = nullptr;
+    n_ = 0;
   }
-  if (keep && *p && cap > 0 &&
-      hipMemcpy(q, *p, cap * sizeof(T), hipMemcpyDeviceToDevice) != hipSuccess) {
-    (void)hipFree(q);
-    set_error("hipMemcpy failed (fit scratch grow)");
-    return SF_EIO;
+  void swap(DevBuf& o) {
+    std::swap(p_, o.p_);
+    std::swap(n_, o.n_);
   }
-  if (*p) (void)hipFree(*p);
-  *p = q;
-  cap = need;
-  return SF_OK;
+
+  // At least `need` elements, contents not kept: the old buffer is freed
+  // before the new one (exactly `need`) is allocated, so the two never
+  // coexist.  A failure leaves the buffer empty.
+  int reserve(size_t need, const char* what) {
+    if (n_ >= need) return SF_OK;
+    reset();
+    if (hipMalloc(reinterpret_cast<void**>(&p_), need * sizeof(T)) != hipSuccess) {
+      p_ = nullptr;
+      set_error(what);
+      return SF_ENOMEM;
+    }
+    n_ = need;
+    return SF_OK;
+  }
+
+  // At least `need` elements with the old ones copied over (the caller has
+  // synchronised the streams that write them).  Old and new coexist during
+  // the copy; a failure leaves the old buffer as it was.
+  int reserve_keep(size_t need, const char* what) {
+    if (n_ >= need) return SF_OK;
+    DevBuf q;
+    SF_TRY(q.reserve(need, what));
+    if (n_ > 0 && hipMemcpy(q.p_, p_, n_ * sizeof(T), hipMemcpyDeviceToDevice) != hipSuccess) {
+      set_error(std::string(what) + " (copy of the old contents)");
+      return SF_EIO;
+    }
+    swap(q);
+    return SF_OK;
+  }
+
+ private:
+  T* p_ = nullptr;
+  size_t n_ = 0;
+};
+
+// Two buffers sized together: when either is too small both are freed before
+// either is allocated, so the old and the new pair never coexist.
+template <typename T, typename U>
+int reserve_pair(DevBuf<T>& p, size_t np, DevBuf<U>& q, size_t nq, const char* what) {
+  if (p.size() >= np && q.size() >= nq) return SF_OK;
+  p.reset();
+  q.reset();
+  SF_TRY(p.reserve(np, what));
+  return q.reserve(nq, what);
 }
 
-// Two buffers sized together, replaced, not kept: both are freed before
-// either is allocated, so the old and the new pair never coexist.  `cap` is
-// the pair's size in the caller's unit (0 while either buffer is missing).
-template <typename T, typename U>
-int replace_pair(size_t& cap, size_t new_cap, T** p, size_t np, U** q, size_t nq) {
-  if (*p) (void)hipFree(*p);
-  if (*q) (void)hipFree(*q);
-  *p = nullptr;
-  *q = nullptr;
-  cap = 0;
-  size_t cp = 0, cq = 0;
-  SF_TRY_RC(grow(p, cp, np));
-  SF_TRY_RC(grow(q, cq, nq));
-  cap = new_cap;
-  return SF_OK;
-}
+// what a failed allocation of the fit's tables, pool and scratch reports
+constexpr const char* kFitAlloc = "hipMalloc failed (fit scratch)";
 
 // A kernel launched with more than 64 KiB of dynamic LDS has to be allowed it
 template <typename K>
@@ -134,51 +170,45 @@ struct sf_ctx {
                                // D > SF_MAX_DIR (kl_fit_wide.hip fits it)
   double r0 = 100.0;
   double beta = 5.0 / 3.0;
-  double* d_pp = nullptr;      // [D][3]
-  double* d_c = nullptr;       // [D][D]
-  double* d_pinv = nullptr;    // [D][D]
-  double* d_u = nullptr;       // [D][D] (columns sorted by |lambda| desc)
-  double* d_eig = nullptr;     // [D]    (signed eigenvalues, sorted)
+  sf::DevBuf<double> d_pp;      // [D][3]
+  sf::DevBuf<double> d_c;       // [D][D]
+  sf::DevBuf<double> d_pinv;    // [D][D]
+  sf::DevBuf<double> d_u;       // [D][D] (columns sorted by |lambda| desc)
+  sf::DevBuf<double> d_eig;     // [D]    (signed eigenvalues, sorted)
   // wide fit (kl_fit_wide.hip): the matrices of the basis kernel, then of the
   // fit workgroups that do not fit the LDS
-  double* d_wide_ws = nullptr;
-  size_t wide_ws_cap = 0;      // doubles
+  sf::DevBuf<double> d_wide_ws;
   // mask cache of the wide fit: every distinct flag mask of a call's input is
   // decomposed once (128-bit keys; rebuilt by every sf_kl_fit)
   int wide_cache = 1;          // SF_OPT_FIT_WIDE_CACHE
   int wide_pool_mb = 0;        // SF_OPT_FIT_WIDE_POOL_MB (0 = 2048)
   int wide_pool_max = 0;       // SF_OPT_FIT_WIDE_POOL_MAX (0 = no entry cap)
-  unsigned long long* d_wkeys = nullptr;  // [S][2] initial mask of every slot
-  int* d_wslot = nullptr;      // [S] table slot, then pool id, of that mask
-  size_t wslot_cap = 0;        // slots
-  unsigned long long* d_wtab = nullptr;   // [wtab_cap] claimant slot + 1 (0 = empty)
-  int* d_wtab_id = nullptr;    // [wtab_cap] pool id of a claimed table entry
-  size_t wtab_cap = 0;         // power of two
-  unsigned long long* d_wpool_mask = nullptr;  // [entries][2]
-  size_t wpool_mask_cap = 0;   // words (two per entry)
-  double* d_wpool = nullptr;   // [wide_pool_n][D (D | 1) + 2 D]: V, lam, perm
-  size_t wpool_cap = 0;        // doubles
+  sf::DevBuf<unsigned long long> d_wkeys;  // [S][2] initial mask of every slot
+  sf::DevBuf<int> d_wslot;      // [S] table slot, then pool id, of that mask
+  sf::DevBuf<unsigned long long> d_wtab;   // [power of two] claimant slot + 1 (0 = empty)
+  sf::DevBuf<int> d_wtab_id;    // [as d_wtab] pool id of a claimed table entry
+  sf::DevBuf<unsigned long long> d_wpool_mask;  // [entries][2]
+  sf::DevBuf<double> d_wpool;   // [wide_pool_n][D (D | 1) + 2 D]: V, lam, perm
   int wide_pool_n = 0;         // entries the last fit built (for this D)
   // pixel grid (sf_set_grid)
   int nx = 0, ny = 0;
   int64_t n_pix = 0;
   int64_t n_pix_blocks = 0;    // workgroup pixel blocks (kBlockPix)
   int ksteps = 0;              // ceil(D / 4)
-  double* d_cfrag = nullptr;   // [wave pixel blocks][ksteps][kTiles][64]
+  sf::DevBuf<double> d_cfrag;   // [wave pixel blocks][ksteps][kTiles][64]
   // fixed-point phase epilogue: a lane's |coef| sum (turns) below rev_thr
   // bounds its phases below 2^17 turns (kl_eval_impl.h group_rev_safe)
   double rev_thr = 0.0;
   // integer-digit contraction (kl_eval_int.h): Cpix as 6 balanced base-256
   // digits of rint(Cpix * 2^36) in i8 MFMA B-fragment order (phase screens,
   // D >= 45), and whether the grid fits the digits
-  int8_t* d_cdig = nullptr;    // [wave pixel blocks][6][kTiles][64][16 B]
+  sf::DevBuf<int8_t> d_cdig;    // [wave pixel blocks][6][kTiles][64][16 B]
   int dig_ok = 0;              // 1: max |Cpix| * 2^36 fits 6 digits
   int eval_int = -1;           // SF_OPT_EVAL_INT (-1 auto, 0 off)
   int eval_wg_waves = 0;       // SF_OPT_EVAL_WG_WAVES (0 = 4, or 8)
   // per-call slot digits of the integer contraction (kl_kdig_kernel)
-  int8_t* d_kdig = nullptr;    // [slot][6][64]
-  uint8_t* d_kflag = nullptr;  // [slot]: 1 = integer path
-  int64_t kdig_slots = 0;      // slots the buffers hold
+  sf::DevBuf<int8_t> d_kdig;    // [slot][6][64]
+  sf::DevBuf<uint8_t> d_kflag;  // [slot]: 1 = integer path
   // recorded after every launch that reads d_kdig / d_kflag: the next
   // prepass (on whatever stream) waits for it before rewriting them
   hipEvent_t kdig_read = nullptr;
@@ -188,57 +218,42 @@ struct sf_ctx {
   int pt_tiles = 0;            // 16-point tiles, padded to whole passes
   int pt_ks_pad = 0;           // k-steps, padded to the k-loop's trip
   int pt_cus = 0;              // compute units of the device
-  double* d_pxy = nullptr;     // [P][2]
-  double* d_pfrag = nullptr;   // [pt_tiles][pt_ks_pad][64] MFMA B fragments
+  sf::DevBuf<double> d_pxy;     // [P][2]
+  sf::DevBuf<double> d_pfrag;   // [pt_tiles][pt_ks_pad][64] MFMA B fragments
   // output channels of sf_kl_eval_tec (sf_set_tec_freqs, kl_tec.hip), grouped
   // by TEC frequency; independent of the geometry
   int tec_F = 0;               // channels bound (0: none)
   int tec_F_tec = 0;           // TEC frequencies of the coefficient arrays
   std::vector<int> tec_used;   // the TEC frequencies that have channels, ascending
   std::vector<int> tec_off;    // [used + 1] their ranges in the lists
-  double* d_tec_ch = nullptr;  // [F] scale in turns per TECU, then [F] int
+  sf::DevBuf<double> d_tec_ch;  // [F] scale in turns per TECU, then [F] int
                                // channel index, both in list order
   // fit scratch
-  uint8_t* d_skip = nullptr;   // [F][A] block skip flags
-  size_t skip_cap = 0;
-  int* d_st_order = nullptr;   // [A]
-  size_t st_order_cap = 0;
+  sf::DevBuf<uint8_t> d_skip;   // [F][A] block skip flags
+  sf::DevBuf<int> d_st_order;   // [A]
   // mask-keyed cache of flagged-subset bases (kl_fit_fast.hip)
-  unsigned long long* d_keys = nullptr;  // hash table keys (0 = empty)
-  int* d_ids = nullptr;                  // hash table values (-1 = unassigned)
-  size_t table_cap = 0;                  // power of two
-  unsigned long long* d_pool_mask = nullptr;  // [pool_cap] mask of pool entry
-  double* d_pool = nullptr;              // [pool_cap][D*D + D] (U_sub, lam)
+  sf::DevBuf<unsigned long long> d_keys;  // [power of two] hash table keys (0 = empty)
+  sf::DevBuf<int> d_ids;                  // [as d_keys] hash table values (-1 = unassigned)
+  sf::DevBuf<unsigned long long> d_pool_mask;  // [pool entries] mask of pool entry
+  sf::DevBuf<double> d_pool;              // [pool entries][D*D + D] (U_sub, lam)
   int fit_eig_waves = 0;                 // SF_OPT_FIT_EIG_WAVES (0 = 3)
   int fit_subset_deletion = 1;           // SF_OPT_FIT_SUBSET_DELETION: 1 from ancestors (default), 2 from the global basis, 0 Jacobi
-  size_t pool_cap = 0;
-  uint8_t* d_pool_status = nullptr;      // [>= pool entries] deletion kernel: 0 done, 1 Jacobi
-  size_t pool_status_cap = 0;
+  sf::DevBuf<uint8_t> d_pool_status;      // [>= pool entries] deletion kernel: 0 done, 1 Jacobi
   int pool_D = 0;
-  int* d_pos = nullptr;                  // [S] table slot of the current mask
-  uint8_t* d_class = nullptr;            // [S] 0 fast, 1 skipped, 2 slow, 3 lane
-  long long* d_list = nullptr;           // [S] work list of the fast pass (kl_fit_lane.h)
-  size_t list_cap = 0;
-  double* d_sigma = nullptr;             // [F][A] tec/amplitude block sigma
-  size_t sigma_cap = 0;
-  size_t slot_cap = 0;
-  int* d_counters = nullptr;  // [kFitCounters], indexed by sf::FitCounter
-  size_t counters_cap = 0;
-  double* d_scratch = nullptr;           // resid / state when caller passes NULL
-  size_t scratch_cap = 0;
-  float* d_wscratch = nullptr;           // w_out / order_out likewise
-  size_t wscratch_cap = 0;
-  int32_t* d_oscratch = nullptr;
-  size_t oscratch_cap = 0;
+  sf::DevBuf<int> d_pos;                  // [S] table slot of the current mask
+  sf::DevBuf<uint8_t> d_class;            // [S] 0 fast, 1 skipped, 2 slow, 3 lane
+  sf::DevBuf<long long> d_list;           // [S] work list of the fast pass (kl_fit_lane.h)
+  sf::DevBuf<double> d_sigma;             // [F][A] tec/amplitude block sigma
+  sf::DevBuf<int> d_counters;  // [kFitCounters], indexed by sf::FitCounter
+  sf::DevBuf<double> d_scratch;           // resid / state when caller passes NULL
+  sf::DevBuf<float> d_wscratch;           // w_out / order_out likewise
+  sf::DevBuf<int32_t> d_oscratch;
   // Gaussian weights of sf_tess_fill / sf_smooth, pass buffer of sf_smooth
-  double* d_gw = nullptr;
-  size_t gw_cap = 0;                     // doubles
+  sf::DevBuf<double> d_gw;
   double gw_sigma = -1.0;                // sigma whose weights d_gw holds
-  float* d_trash = nullptr;  // 1 KiB sink of the eval's out-of-range stores
-  float* d_smooth = nullptr;
-  size_t smooth_cap = 0;                 // bytes
-  float* d_tess_tab = nullptr;           // tessellated value table [S][D+1][4]
-  size_t tess_tab_cap = 0;               // bytes
+  sf::DevBuf<float> d_trash;  // 1 KiB sink of the eval's out-of-range stores
+  sf::DevBuf<float> d_smooth;
+  sf::DevBuf<float> d_tess_tab;           // tessellated value table [S][D+1][4]
   // fast-path switch (SCREENFIT_FIT=general forces the general kernel)
   int force_general = 0;
   // evaluation kernel (SF_OPT_EVAL_KERNEL)

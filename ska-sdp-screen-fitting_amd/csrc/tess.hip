@@ -688,23 +688,6 @@ __global__ __launch_bounds__(256) void smooth_pass_kernel(
 
 // ---------------------------------------------------------------- host ----
 
-// A grow-only scratch buffer of the context (the value table, the pass
-// buffer): at least `need` bytes.  The old buffer is freed before the new one
-// is allocated, so the two never coexist; a failed allocation leaves none.
-template <class T>
-static int scratch_reserve(T** buf, size_t* cap, size_t need, const char* what) {
-  if (*cap >= need) return SF_OK;
-  if (*buf) (void)hipFree(*buf);
-  *buf = nullptr;
-  *cap = 0;
-  if (hipMalloc(reinterpret_cast<void**>(buf), need) != hipSuccess) {
-    set_error(what);
-    return SF_ENOMEM;
-  }
-  *cap = need;
-  return SF_OK;
-}
-
 // Workgroups of `threads` for n_items work items: one each up to the dispatch
 // limit (2^32 work-items, kept at 2^31); past it the workgroups walk the rest
 static unsigned walk_grid(int64_t n_items, int threads) {
@@ -721,8 +704,8 @@ int launch_smooth(sf_ctx* ctx, float* cube, int nx, int ny, int64_t n_img,
   if (chunk < 4) chunk = 4;
   chunk &= ~(int64_t)3;  // whole [4][ny][nx] slot cubes (plane = img % 4)
   if (chunk > n_img) chunk = n_img;
-  SF_TRY_RC(scratch_reserve(&ctx->d_smooth, &ctx->smooth_cap, (size_t)(chunk * P) * sizeof(float),
-                            "sf_smooth: hipMalloc of the pass buffer failed"));
+  SF_TRY(ctx->d_smooth.reserve((size_t)(chunk * P),
+                               "sf_smooth: hipMalloc of the pass buffer failed"));
   for (int64_t i0 = 0; i0 < n_img; i0 += chunk) {
     const int64_t ni = (n_img - i0 < chunk) ? n_img - i0 : chunk;
     const int64_t n = ni * P;
@@ -883,9 +866,9 @@ int launch_tess(sf_ctx* ctx, const int32_t* labels, int nx, int ny,
   int64_t per = (((int64_t)256 << 20) / (DT * 16)) / p.chunk * p.chunk;
   if (per < p.chunk) per = p.chunk;
   if (per > S) per = S;
-  SF_TRY_RC(scratch_reserve(&ctx->d_tess_tab, &ctx->tess_tab_cap, (size_t)(per * DT) * 16,
-                            "sf_tess_fill: hipMalloc of the value table failed"));
-  tess_v4f* tab = reinterpret_cast<tess_v4f*>(ctx->d_tess_tab);
+  SF_TRY(ctx->d_tess_tab.reserve((size_t)(per * DT) * 4,
+                                 "sf_tess_fill: hipMalloc of the value table failed"));
+  tess_v4f* tab = reinterpret_cast<tess_v4f*>(ctx->d_tess_tab.get());
   for (int64_t b = 0; b < S; b += per) {
     const int64_t Sb = S - b < per ? S - b : per;
     hipLaunchKernelGGL(kl_tess_table_kernel, dim3((unsigned)((Sb * DT + 255) / 256)),
