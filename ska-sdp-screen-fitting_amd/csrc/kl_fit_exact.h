@@ -159,7 +159,10 @@ __device__ void fit_screen(const Team& tm, const X& L, const Subset& st, int D,
     v2[lp] = w_p;
   }
   tm.sync();
-  const Tie2 tie(n, K, v0, v1, v2);
+  double tie_lam[2] = {0.0, 0.0};
+  if (n == 2)
+    for (int k = 0; k < 2; ++k) tie_lam[k] = st.full ? L.eigv(k) : L.lam[k];
+  const Tie2 tie(n, K, v0, v1, v2, tie_lam);
   // rr1 = U_k^T W r (lane k < K);  G = U_k^T W U_k (row k, the columns split
   // between the shares)
   double g1 = 0.0, g2 = 0.0;

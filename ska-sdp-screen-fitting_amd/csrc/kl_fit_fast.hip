@@ -190,7 +190,8 @@ __device__ void fit_once(const FastLds& L, const Basis& B, int D, int ld,
     v2[l] = w_p;
   }
   lds_sync();
-  const Tie2 tie(n, K, v0, v1, v2);  // two unflagged directions: U_k = e_2
+  // two unflagged directions whose tie passes the cutoff: U_k = e_2
+  const Tie2 tie(n, K, v0, v1, v2, B.lam);
   double a1 = 0.0, a2 = 0.0;
   if (l < K) {
 #pragma unroll kMatVecUnroll

@@ -216,16 +216,25 @@ __device__ __forceinline__ bool flag_circular_outliers(const Team& tm, bool live
 // leaves rounding residue there give atan2 of that residue instead).
 // Taken from rc = W cos / W x, rs = W sin and w of the gathered directions
 // before those vectors are overwritten.
+// Only while the pair's eigenvalues (lam: those of the slot's basis, +-b)
+// pass the pinv cutoff: at |b| <= 1e-3 (a pair closer than ~2.4
+// piercepoint units at r_0 = 100, or a large r_0) the reference's pinv(C) is 0, and the slot goes
+// the ordinary way, whose `keep` tests leave the screen and the coefficients
+// at +0 and the residual at the values (tests/golden/make_golden_near.py).
 struct Tie2 {
   bool on;
   double t_re = 0.0, t_im = 0.0;
   __device__ __forceinline__ Tie2(int n, int K, const double* rc,
-                                  const double* rs, const double* w)
-      : on(n == 2 && K == 1) {
+                                  const double* rs, const double* w,
+                                  const double* lam)
+      : on(n == 2 && K == 1 && fabs(lam[0]) > kPinvAtol &&
+           fabs(lam[1]) > kPinvAtol) {
 #pragma clang fp contract(off)
-    if (on) {
-      const double w2 = w[1];
-      const double iw = w2 > kPinvAtol ? 1.0 / w2 : 0.0;
+    // w_2 at or below the cutoff: inv_u = 0 and t stays (+0, +0) -- not
+    // 0 * rc, whose zero takes the sign of cos(phi_2) and would make
+    // atan2(0, -0) = pi where the reference's screen is 0 (near_tie4.npz)
+    if (on && w[1] > kPinvAtol) {
+      const double iw = 1.0 / w[1];
       t_re = iw * rc[1];
       t_im = iw * rs[1];
     }
