@@ -23,6 +23,7 @@ from ._lib import (SF_EVAL_BIG_ENDIAN, SF_EVAL_FAST_SINCOS, SF_EVAL_NAN_SCRUB,
                    SF_EVAL_NT_STORES, SF_MAX_DIR, SF_MAX_POINTS, Context)
 from .h5parm import H5parm, get_reference_station
 from .screen import Screen, canonical_axes, phase_pols
+from .streaming import batch_rows, stream_time_rows
 
 # NaN scrub (screen.py:368-378) + exact fp64 reduction of the phase in
 # revolutions / hardware fp32 sincos + streaming stores
@@ -90,13 +91,36 @@ class KLEvaluator:
             if x_coord is not None:
                 self.ctx.set_grid(x_coord, y_coord)
 
+    def _launch(self, call, out_dev=None, shape=None, dtype=None):
+        """``call(out_dev)`` on this evaluator's device, its context bound to
+        the current stream; ``out_dev`` is allocated unless given (``shape``,
+        float32 unless ``dtype``) and returned."""
+        torch = self.torch
+        if out_dev is None and shape is not None:
+            out_dev = torch.empty(shape, dtype=dtype or torch.float32, device=self.dev)
+        with torch.cuda.device(self.dev):
+            self.ctx.set_stream(torch.cuda.current_stream(self.dev).cuda_stream)
+            call(out_dev)
+        return out_dev
+
+    def _host(self, coef, tail, run):
+        """Host [..., D] coefficients in, host ``lead + tail`` out: ``run``
+        takes the uploaded [S, D] coefficients and returns the device result."""
+        lead = np.shape(coef)[:-1]
+        return run(self._upload(coef)).cpu().numpy().reshape(lead + tail)
+
+    def _upload(self, a, shape=None):
+        """Host array as a float64 device tensor, [S, D] unless ``shape``."""
+        a = np.ascontiguousarray(a, np.float64)
+        return self.torch.from_numpy(a.reshape(shape or (-1, self.D))).to(self.dev)
+
+    def _upload_opt(self, a):
+        return None if a is None else self._upload(a)
+
     def set_points(self, xy):
         """Bind P screen positions ``xy`` [P, 2] (piercepoint coordinates,
         ``geometry.screen_xy``) for ``sample_device`` / ``sample_host``."""
-        torch = self.torch
-        with torch.cuda.device(self.dev):
-            self.ctx.set_stream(torch.cuda.current_stream(self.dev).cuda_stream)
-            self.ctx.set_points(xy)
+        self._launch(lambda _: self.ctx.set_points(xy))
         self.n_points = self.ctx.points
 
     def sample_device(self, coef_dev, xx_dev=None, yy_dev=None, out_dev=None,
@@ -104,62 +128,38 @@ class KLEvaluator:
         """coef_dev: device [S, D] float64 -> device [S, 4, P] float32 Jones
         planes at the bound points (gain planes with ``xx_dev`` / ``yy_dev``),
         or, with ``values``, the screen values [S, P] float64."""
-        torch = self.torch
         S, P = coef_dev.shape[0], self.n_points
-        if out_dev is None:
-            out_dev = (torch.empty((S, P), dtype=torch.float64, device=self.dev)
-                       if values else
-                       torch.empty((S, 4, P), dtype=torch.float32, device=self.dev))
-        with torch.cuda.device(self.dev):
-            self.ctx.set_stream(torch.cuda.current_stream(self.dev).cuda_stream)
-            if values:
-                self.ctx.eval_point_values(coef_dev, S, out_dev)
-            else:
-                self.ctx.eval_points(coef_dev, S, out_dev, xx_dev, yy_dev, flags)
-        return out_dev
+        if values:
+            return self._launch(lambda out: self.ctx.eval_point_values(coef_dev, S, out),
+                                out_dev, (S, P), self.torch.float64)
+        return self._launch(
+            lambda out: self.ctx.eval_points(coef_dev, S, out, xx_dev, yy_dev, flags),
+            out_dev, (S, 4, P))
 
     def sample_host(self, coef, amp_xx=None, amp_yy=None, values=False,
                     flags=SF_EVAL_NAN_SCRUB | SF_EVAL_FAST_SINCOS):
         """Host [..., D] coefficients -> host float32 [..., 4, P] planes, or
         float64 [..., P] values."""
-        coef = np.asarray(coef)
-        lead = coef.shape[:-1]
-        c = self._upload(coef)
         if values:
-            out = self.sample_device(c, values=True)
-            return out.cpu().numpy().reshape(lead + (self.n_points,))
-        if amp_xx is None:
-            out = self.sample_device(c, flags=flags)
-        else:
-            out = self.sample_device(c, self._upload(amp_xx), self._upload(amp_yy),
-                                     flags=flags)
-        return out.cpu().numpy().reshape(lead + (4, self.n_points))
+            return self._host(coef, (self.n_points,),
+                              lambda c: self.sample_device(c, values=True))
+        return self._host(coef, (4, self.n_points), lambda c: self.sample_device(
+            c, self._upload_opt(amp_xx), self._upload_opt(amp_yy), flags=flags))
 
     def eval_device(self, coef_dev, out_dev=None, flags=DEFAULT_FLAGS):
         """coef_dev: device [S, D] float64 -> device [S, 4, ny, nx] float32."""
-        torch = self.torch
         S = coef_dev.shape[0]
-        if out_dev is None:
-            out_dev = torch.empty((S, 4, self.ny, self.nx), dtype=torch.float32,
-                                  device=self.dev)
-        with torch.cuda.device(self.dev):
-            self.ctx.set_stream(torch.cuda.current_stream(self.dev).cuda_stream)
-            self.ctx.eval(coef_dev, S, out_dev, S, flags)
-        return out_dev
+        return self._launch(lambda out: self.ctx.eval(coef_dev, S, out, S, flags),
+                            out_dev, (S, 4, self.ny, self.nx))
 
     def eval_gain_device(self, coef_dev, xx_dev, yy_dev, out_dev=None,
                          flags=DEFAULT_FLAGS):
         """Phase + XX / YY log10-amplitude coefficients (device [S, D] each)
         -> device [S, 4, ny, nx] gain planes."""
-        torch = self.torch
         S = coef_dev.shape[0]
-        if out_dev is None:
-            out_dev = torch.empty((S, 4, self.ny, self.nx), dtype=torch.float32,
-                                  device=self.dev)
-        with torch.cuda.device(self.dev):
-            self.ctx.set_stream(torch.cuda.current_stream(self.dev).cuda_stream)
-            self.ctx.eval_gain(coef_dev, xx_dev, yy_dev, S, out_dev, S, flags)
-        return out_dev
+        return self._launch(
+            lambda out: self.ctx.eval_gain(coef_dev, xx_dev, yy_dev, S, out, S, flags),
+            out_dev, (S, 4, self.ny, self.nx))
 
     def eval_pol_device(self, xx_dev, yy_dev, out_dev=None, amp_xx_dev=None,
                         amp_yy_dev=None, flags=DEFAULT_FLAGS):
@@ -167,28 +167,19 @@ class KLEvaluator:
         coefficients (device [S, D] each), and optionally the XX and YY
         log10-amplitude coefficients (both or neither) -> device
         [S, 4, ny, nx]: planes 0 / 1 from XX, planes 2 / 3 from YY."""
-        torch = self.torch
         S = xx_dev.shape[0]
-        if out_dev is None:
-            out_dev = torch.empty((S, 4, self.ny, self.nx), dtype=torch.float32,
-                                  device=self.dev)
-        with torch.cuda.device(self.dev):
-            self.ctx.set_stream(torch.cuda.current_stream(self.dev).cuda_stream)
-            self.ctx.eval_pol(xx_dev, yy_dev, S, out_dev, S, amp_xx_dev, amp_yy_dev,
-                              flags)
-        return out_dev
+        return self._launch(
+            lambda out: self.ctx.eval_pol(xx_dev, yy_dev, S, out, S, amp_xx_dev,
+                                          amp_yy_dev, flags),
+            out_dev, (S, 4, self.ny, self.nx))
 
     def eval_pol_host(self, coef_xx, coef_yy, amp_xx=None, amp_yy=None,
                       flags=DEFAULT_FLAGS):
         """XX / YY phase coefficients (and optional log10-amplitude coefs):
         host [..., D] -> host float32 [..., 4, ny, nx]."""
-        coef_xx = np.asarray(coef_xx)
-        lead = coef_xx.shape[:-1]
-        out = self.eval_pol_device(
-            self._upload(coef_xx), self._upload(coef_yy),
-            amp_xx_dev=None if amp_xx is None else self._upload(amp_xx),
-            amp_yy_dev=None if amp_yy is None else self._upload(amp_yy), flags=flags)
-        return out.cpu().numpy().reshape(lead + (4, self.ny, self.nx))
+        return self._host(coef_xx, (4, self.ny, self.nx), lambda c: self.eval_pol_device(
+            c, self._upload(coef_yy), amp_xx_dev=self._upload_opt(amp_xx),
+            amp_yy_dev=self._upload_opt(amp_yy), flags=flags))
 
     def values_device(self, coef_dev, out_dev=None, flags=0):
         """coef_dev: device [S, D] float64 -> device [S, ny, nx] float32, the
@@ -196,22 +187,14 @@ class KLEvaluator:
         fp64 contraction, one cast; NaN where a coefficient is NaN unless
         ``flags`` scrub it to 0; plain stores: streaming stores measured no
         faster for this kernel)."""
-        torch = self.torch
         S = coef_dev.shape[0]
-        if out_dev is None:
-            out_dev = torch.empty((S, self.ny, self.nx), dtype=torch.float32,
-                                  device=self.dev)
-        with torch.cuda.device(self.dev):
-            self.ctx.set_stream(torch.cuda.current_stream(self.dev).cuda_stream)
-            self.ctx.eval_values(coef_dev, S, out_dev, S, flags)
-        return out_dev
+        return self._launch(lambda out: self.ctx.eval_values(coef_dev, S, out, S, flags),
+                            out_dev, (S, self.ny, self.nx))
 
     def values_host(self, coef, flags=0):
         """Host [..., D] coefficients -> host float32 [..., ny, nx] values."""
-        coef = np.asarray(coef)
-        lead = coef.shape[:-1]
-        out = self.values_device(self._upload(coef), flags=flags)
-        return out.cpu().numpy().reshape(lead + (self.ny, self.nx))
+        return self._host(coef, (self.ny, self.nx),
+                          lambda c: self.values_device(c, flags=flags))
 
     def eval_tec_device(self, tec_dev, rad_per_tecu, tec_index=None, phase_dev=None,
                         out_dev=None, flags=DEFAULT_FLAGS):
@@ -223,7 +206,6 @@ class KLEvaluator:
         -> device [T, F, A, 4, ny, nx] float32 of the phase
         ``rad_per_tecu[f] * dTEC + phi0``.  One contraction per (time, TEC
         frequency, station); no coefficients are replicated per channel."""
-        torch = self.torch
         if tec_dev.dim() != 4 or tec_dev.shape[3] != self.D:
             raise ValueError(f"tec_dev: shape {tuple(tec_dev.shape)}, expected "
                              f"(T, F_tec, A, {self.D})")
@@ -237,14 +219,12 @@ class KLEvaluator:
         if phase_dev is not None and phase_dev.shape != tec_dev.shape:
             raise ValueError(f"phase_dev: shape {tuple(phase_dev.shape)}, expected "
                              f"{tuple(tec_dev.shape)}")
-        if out_dev is None:
-            out_dev = torch.empty((T, k.size, A, 4, self.ny, self.nx),
-                                  dtype=torch.float32, device=self.dev)
-        with torch.cuda.device(self.dev):
-            self.ctx.set_stream(torch.cuda.current_stream(self.dev).cuda_stream)
+
+        def call(out):
             self._bind_tec_freqs(k, tec_index, F_tec)
-            self.ctx.eval_tec(tec_dev, T, A, out_dev, phase_dev, flags)
-        return out_dev
+            self.ctx.eval_tec(tec_dev, T, A, out, phase_dev, flags)
+
+        return self._launch(call, out_dev, (T, k.size, A, 4, self.ny, self.nx))
 
     def _bind_tec_freqs(self, k, tec_index, F_tec):
         """sf_set_tec_freqs unless this binding is the context's already (it
@@ -260,45 +240,94 @@ class KLEvaluator:
                       flags=DEFAULT_FLAGS):
         """Host [T, F_tec, A, D] TEC (and optional phase) coefficients -> host
         float32 [T, F, A, 4, ny, nx] (``eval_tec_device``)."""
-        torch = self.torch
-
-        def up(a):
-            return torch.from_numpy(np.ascontiguousarray(a, np.float64)).to(self.dev)
-
-        out = self.eval_tec_device(up(tec_coef), rad_per_tecu, tec_index,
-                                   None if phase_coef is None else up(phase_coef),
-                                   flags=flags)
+        out = self.eval_tec_device(
+            self._upload(tec_coef, np.shape(tec_coef)), rad_per_tecu, tec_index,
+            None if phase_coef is None else self._upload(phase_coef, np.shape(phase_coef)),
+            flags=flags)
         return out.cpu().numpy()
 
     def smooth_device(self, out_dev, smooth_pix, flags):
         """Screen.write's Gaussian (screen.py:353-362) in place on a device
         cube [S, 4, ny, nx]; scrub / byte swap in ``flags`` after it."""
-        torch = self.torch
-        with torch.cuda.device(self.dev):
-            self.ctx.set_stream(torch.cuda.current_stream(self.dev).cuda_stream)
-            self.ctx.smooth(out_dev, self.nx, self.ny, 4 * out_dev.shape[0],
-                            smooth_pix, flags)
-        return out_dev
-
-    def _upload(self, a):
-        a = np.ascontiguousarray(a, np.float64)
-        return self.torch.from_numpy(a.reshape(-1, self.D)).to(self.dev)
+        return self._launch(
+            lambda out: self.ctx.smooth(out, self.nx, self.ny, 4 * out.shape[0],
+                                        smooth_pix, flags), out_dev)
 
     def eval_host(self, coef, amp_xx=None, amp_yy=None, flags=DEFAULT_FLAGS):
         """coef (and optional log10-amplitude coefs): host [..., D] -> host
         float32 [..., 4, ny, nx]."""
-        coef = np.asarray(coef)
-        lead = coef.shape[:-1]
-        c = self._upload(coef)
         if amp_xx is None:
-            out = self.eval_device(c, flags=flags)
-        else:
-            out = self.eval_gain_device(c, self._upload(amp_xx),
-                                        self._upload(amp_yy), flags=flags)
-        return out.cpu().numpy().reshape(lead + (4, self.ny, self.nx))
+            return self._host(coef, (4, self.ny, self.nx),
+                              lambda c: self.eval_device(c, flags=flags))
+        return self._host(coef, (4, self.ny, self.nx), lambda c: self.eval_gain_device(
+            c, self._upload(amp_xx), self._upload(amp_yy), flags=flags))
 
 
-class KLScreen(Screen):
+class KLBase(Screen):
+    """What the KL screen classes share: the geometry a fit leaves on the
+    screen soltab, and the grid evaluator built from it."""
+
+    def __init__(self, *args, **kwargs):
+        super().__init__(*args, **kwargs)
+        self.height = None
+        self.beta_val = None
+        self.r_0 = None
+        self.piercepoints = None
+        self.mid_ra = None
+        self.mid_dec = None
+        self.ref_ind = None
+        self._evaluators = {}
+
+    def _check_sky_model(self, dirs):
+        """KeyError (as the reference raises, kl_screen.py:79) for directions
+        the sky model, if there is one, has no patch for."""
+        if self.input_skymodel_filename is not None:
+            patches = set(read_patch_names(self.input_skymodel_filename))
+            missing = [d for d in dirs if d.strip("[]") not in patches]
+            if missing:
+                raise KeyError(f"directions not in the sky model: {missing}")
+
+    def _adopt_screen_soltab(self, st, solset):
+        """The axes and attributes of the fitted screen soltab ``st``; its
+        values (``vals_ph``) are the caller's to shape."""
+        self.times_ph = np.asarray(st.time)
+        self.freqs_ph = np.asarray(st.freq)
+        self.source_names = st.dir
+        self.source_dict = solset.get_source()
+        self.source_positions = [self.source_dict[s] for s in self.source_names]
+        self.station_names = st.ant
+        self.station_dict = solset.get_ant()
+        self.station_positions = [self.station_dict[s] for s in self.station_names]
+        self.height = st.attrs["height"]
+        self.beta_val = st.attrs["beta"]
+        self.r_0 = st.attrs["r_0"]
+        self.piercepoints = np.array(st.piercepoint)
+        self.mid_ra = st.attrs["midra"]
+        self.mid_dec = st.attrs["middec"]
+
+    def _memory_usage(self, cellsize_deg, n_freq, planes):
+        """GB per time slot of a [1, n_freq, A, planes, ny, nx] array, the
+        reference's estimate (kl_screen.py:157-190: int() sizes, 8-byte
+        values, /10 overhead, x ncpu) so that time chunking matches."""
+        ncpu = self.ncpu or multiprocessing.cpu_count()
+        ximsize = int(self.width_ra / cellsize_deg)
+        yimsize = int(self.width_dec / cellsize_deg)
+        nbytes = 8 * n_freq * len(self.station_names) * planes * yimsize * ximsize
+        return nbytes / 1024 ** 3 / 10 * ncpu
+
+    def evaluator(self, cellsize_deg):
+        key = float(cellsize_deg)
+        ev = self._evaluators.get(key)
+        if ev is None:
+            x, y = geometry.grid_coords(self.rad, self.dec, self.width_ra,
+                                        cellsize_deg, self.mid_ra, self.mid_dec)
+            ev = KLEvaluator(self.piercepoints, self.r_0, self.beta_val, x, y,
+                             self.device)
+            self._evaluators = {key: ev}
+        return ev
+
+
+class KLScreen(KLBase):
     """Class for KL (Karhunen-Lo`eve) screens (kl_screen.py:22)."""
 
     def __init__(self, name, h5parm_filename, skymodel_filename, rad, dec,
@@ -308,16 +337,8 @@ class KLScreen(Screen):
                          width_ra, width_dec, solset_name=solset_name,
                          phase_soltab_name=phase_soltab_name,
                          amplitude_soltab_name=amplitude_soltab_name)
-        self.height = None
-        self.beta_val = None
-        self.r_0 = None
-        self.piercepoints = None
-        self.mid_ra = None
-        self.mid_dec = None
-        self._evaluators = {}
         self._sampler = None
         self.solset = None
-        self.ref_ind = None
 
     def fit(self):
         """Fit screens to the input solutions (kl_screen.py:61-155): phases
@@ -335,11 +356,7 @@ class KLScreen(Screen):
         soltab_ph = solset.get_soltab(self.input_phase_soltab_name)
         dirs = [str(d) for d in soltab_ph.dir]
         self.pol_phases = phase_pols(soltab_ph) == 2
-        if self.input_skymodel_filename is not None:
-            patches = set(read_patch_names(self.input_skymodel_filename))
-            missing = [d for d in dirs if d.strip("[]") not in patches]
-            if missing:  # the reference raises KeyError here (kl_screen.py:79)
-                raise KeyError(f"directions not in the sky model: {missing}")
+        self._check_sky_model(dirs)
         ref_ind = get_reference_station(soltab_ph, 10)
         screen_order = min(20, len(dirs) - 1)
         stationscreen.run(soltab_ph, "phase_screen000", order=screen_order,
@@ -358,20 +375,7 @@ class KLScreen(Screen):
             self.freqs_amp = np.asarray(sta.freq)
         st = solset.get_soltab("phase_screen000")
         self.vals_ph = canonical_axes(st, st.val)
-        self.times_ph = np.asarray(st.time)
-        self.freqs_ph = np.asarray(st.freq)
-        self.source_names = st.dir
-        self.source_dict = solset.get_source()
-        self.source_positions = [self.source_dict[s] for s in self.source_names]
-        self.station_names = st.ant
-        self.station_dict = solset.get_ant()
-        self.station_positions = [self.station_dict[s] for s in self.station_names]
-        self.height = st.attrs["height"]
-        self.beta_val = st.attrs["beta"]
-        self.r_0 = st.attrs["r_0"]
-        self.piercepoints = np.array(st.piercepoint)
-        self.mid_ra = st.attrs["midra"]
-        self.mid_dec = st.attrs["middec"]
+        self._adopt_screen_soltab(st, solset)
         # the input and screen soltabs (in memory) and the reference station,
         # for patch_errors
         self.solset = solset
@@ -379,24 +383,8 @@ class KLScreen(Screen):
         h5.close()
 
     def get_memory_usage(self, cellsize_deg):
-        """GB per time slot, the reference's estimate (kl_screen.py:157-190:
-        int() sizes, /10 overhead, x ncpu) so that time chunking matches."""
-        ncpu = self.ncpu or multiprocessing.cpu_count()
-        ximsize = int(self.width_ra / cellsize_deg)
-        yimsize = int(self.width_dec / cellsize_deg)
-        nbytes = 8 * len(self.freqs_ph) * len(self.station_names) * 4 * yimsize * ximsize
-        return nbytes / 1024 ** 3 / 10 * ncpu
-
-    def evaluator(self, cellsize_deg):
-        key = float(cellsize_deg)
-        ev = self._evaluators.get(key)
-        if ev is None:
-            x, y = geometry.grid_coords(self.rad, self.dec, self.width_ra,
-                                        cellsize_deg, self.mid_ra, self.mid_dec)
-            ev = KLEvaluator(self.piercepoints, self.r_0, self.beta_val, x, y,
-                             self.device)
-            self._evaluators = {key: ev}
-        return ev
+        """GB per time slot of the Jones cube (``_memory_usage``)."""
+        return self._memory_usage(cellsize_deg, len(self.freqs_ph), 4)
 
     def make_matrix(self, t_start_index, t_stop_index, freq_ind, stat_ind,
                     cellsize_deg, out_dir, ncpu):
@@ -425,51 +413,40 @@ class KLScreen(Screen):
         """All (freq, station) screens of times [g_start, g_stop): device
         batches of whole time rows in FITS byte order, streamed through
         pinned buffers to the file while the next batch is evaluated."""
-        from .streaming import PinnedPipeline
-        torch = __import__("torch")
         ev = self.evaluator(cellsize_deg)
-        vals = np.asarray(self.vals_ph)
-        n_f, n_a, D = vals.shape[1], vals.shape[2], vals.shape[3]
-        per_slot = 16 * ev.nx * ev.ny
-        row_bytes = n_f * n_a * per_slot
-        rows = max(1, int(max_batch_bytes // row_bytes))
-        rows = min(rows, g_stop - g_start)
+        vals = np.asarray(self.vals_ph)[g_start:g_stop]
+        slots = vals.shape[1] * vals.shape[2]  # per time row
         if self.pol_phases:
-            coef = ev._upload(vals[g_start:g_stop, ..., 0])
-            coef_y = ev._upload(vals[g_start:g_stop, ..., 1])
-            c_xx = c_yy = None
+            coef, coef_y = ev._upload(vals[..., 0]), ev._upload(vals[..., 1])
         else:
-            coef = ev._upload(vals[g_start:g_stop])
+            coef = ev._upload(vals)
+        c_xx = c_yy = None
         if not self.phase_only:
             amp = np.asarray(self.vals_amp)[g_start:g_stop]
             c_xx, c_yy = ev._upload(amp[..., 0]), ev._upload(amp[..., 1])
-        pipe = PinnedPipeline(torch, ev.dev, rows * row_bytes)
-        try:
-            for t0 in range(g_start, g_stop, rows):
-                t1 = min(g_stop, t0 + rows)
-                s0, s1 = (t0 - g_start) * n_f * n_a, (t1 - g_start) * n_f * n_a
-                slot, buf = pipe.device_buffer((s1 - s0) * per_slot)
-                out = buf.view(torch.float32).view(s1 - s0, 4, ev.ny, ev.nx)
-                fin = SF_EVAL_NAN_SCRUB | SF_EVAL_BIG_ENDIAN
-                # with smoothing, scrub and byte swap come after the Gaussian
-                # (screen.py:353-378 smooths, then replaces NaNs)
-                flags = DEFAULT_FLAGS | fin if smooth_pix <= 0 else \
-                    DEFAULT_FLAGS & ~SF_EVAL_NAN_SCRUB
-                if self.pol_phases:
-                    # 2 coefficient sets, 4 with the amplitudes
-                    ev.eval_pol_device(coef[s0:s1], coef_y[s0:s1], out,
-                                       None if c_xx is None else c_xx[s0:s1],
-                                       None if c_yy is None else c_yy[s0:s1], flags)
-                elif self.phase_only:
-                    ev.eval_device(coef[s0:s1], out, flags)
-                else:
-                    ev.eval_gain_device(coef[s0:s1], c_xx[s0:s1], c_yy[s0:s1],
-                                        out, flags)
-                if smooth_pix > 0:
-                    ev.smooth_device(out, smooth_pix, fin)
-                pipe.submit(slot, (s1 - s0) * per_slot, writer)
-        finally:
-            pipe.close()
+        fin = SF_EVAL_NAN_SCRUB | SF_EVAL_BIG_ENDIAN
+        # with smoothing, scrub and byte swap come after the Gaussian
+        # (screen.py:353-378 smooths, then replaces NaNs)
+        flags = DEFAULT_FLAGS | fin if smooth_pix <= 0 else \
+            DEFAULT_FLAGS & ~SF_EVAL_NAN_SCRUB
+
+        def evaluate(r0, r1, buf):
+            s = slice(r0 * slots, r1 * slots)
+            out = buf.view(ev.torch.float32).view(-1, 4, ev.ny, ev.nx)
+            if self.pol_phases:
+                # 2 coefficient sets, 4 with the amplitudes
+                ev.eval_pol_device(coef[s], coef_y[s], out,
+                                   None if c_xx is None else c_xx[s],
+                                   None if c_yy is None else c_yy[s], flags)
+            elif self.phase_only:
+                ev.eval_device(coef[s], out, flags)
+            else:
+                ev.eval_gain_device(coef[s], c_xx[s], c_yy[s], out, flags)
+            if smooth_pix > 0:
+                ev.smooth_device(out, smooth_pix, fin)
+
+        stream_time_rows(writer, ev.dev, g_stop - g_start,
+                         slots * 16 * ev.nx * ev.ny, max_batch_bytes, evaluate)
 
     def sampler(self):
         """The evaluator ``sample`` binds its positions on (no pixel grid)."""
@@ -537,7 +514,7 @@ class KLScreen(Screen):
             ev.set_points(xy[sel])
             row_bytes = n_f * n_a * ((8 if values else 16) * P * pols +
                                      8 * D * ((2 if gain else 0) + pols))
-            rows = max(1, int(max_batch_bytes // row_bytes))
+            rows = batch_rows(t_stop - t_start, row_bytes, max_batch_bytes)
             for t0 in range(t_start, t_stop, rows):
                 t1 = min(t_stop, t0 + rows)
                 dst = out[t0 - t_start:t1 - t_start]

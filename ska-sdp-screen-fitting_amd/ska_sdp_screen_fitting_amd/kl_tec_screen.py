@@ -22,18 +22,17 @@ and a frequency-independent scalar-phase soltab over the same directions) the
 gain cube renders ``exp(i (phi0 + tec_to_phase * dTEC / nu))``.
 """
 
-import multiprocessing
 import os
 
 import numpy as np
 
 from . import fits
-from . import geometry
 from . import stationscreen
 from ._lib import SF_EVAL_BIG_ENDIAN, SF_EVAL_NAN_SCRUB
 from .h5parm import H5parm, get_reference_station
-from .kl_screen import DEFAULT_FLAGS, KLEvaluator, read_patch_names
-from .screen import Screen, nearest_index, time_chunks
+from .kl_screen import DEFAULT_FLAGS, KLBase
+from .screen import nearest_index
+from .streaming import stream_time_rows
 
 # phase [rad] = TEC_TO_PHASE * dTEC [TECU] / nu [Hz]: -8.4479745e9 is the usual
 # first-order ionospheric constant (-e^2 / (4 pi eps0 m_e c) * 1e16).  It is
@@ -119,7 +118,7 @@ def check_phase_soltab_axes(soltab_tec, soltab_phase):
                      "length 1")
 
 
-class KLTecScreen(Screen):
+class KLTecScreen(KLBase):
     """KL screens of a ``tec`` soltab (values in TECU)."""
 
     def __init__(self, name, h5parm_filename, skymodel_filename, rad, dec,
@@ -133,14 +132,6 @@ class KLTecScreen(Screen):
         # the frequency-independent scalar phase of a tecandphase solution
         self.input_phi0_soltab_name = phase_soltab_name
         self.vals_phi0 = None  # its screens on tec_screen000's axes, radians
-        self.height = None
-        self.beta_val = None
-        self.r_0 = None
-        self.piercepoints = None
-        self.mid_ra = None
-        self.mid_dec = None
-        self.ref_ind = None
-        self._evaluators = {}
 
     def fit(self):
         """Fit the tec screens as ``KLScreen.fit`` fits phases: reference
@@ -153,11 +144,7 @@ class KLTecScreen(Screen):
         solset = h5.get_solset(self.input_solset_name)
         soltab_tec = solset.get_soltab(self.input_tec_soltab_name)
         dirs = [str(d) for d in soltab_tec.dir]
-        if self.input_skymodel_filename is not None:
-            patches = set(read_patch_names(self.input_skymodel_filename))
-            missing = [d for d in dirs if d.strip("[]") not in patches]
-            if missing:
-                raise KeyError(f"directions not in the sky model: {missing}")
+        self._check_sky_model(dirs)
         ref_ind = get_reference_station(soltab_tec, 10)
         screen_order = min(20, len(dirs) - 1)
         rc = stationscreen.run(soltab_tec, "tec_screen000", order=screen_order,
@@ -182,45 +169,16 @@ class KLTecScreen(Screen):
         st = solset.get_soltab("tec_screen000")
         # (vals_ph / times_ph / freqs_ph: the names Screen.write's chunking reads)
         self.vals_ph = st.val
-        self.times_ph = np.asarray(st.time)
-        self.freqs_ph = np.asarray(st.freq)
-        self.source_names = st.dir
-        self.source_dict = solset.get_source()
-        self.source_positions = [self.source_dict[s] for s in self.source_names]
-        self.station_names = st.ant
-        self.station_dict = solset.get_ant()
-        self.station_positions = [self.station_dict[s] for s in self.station_names]
-        self.height = st.attrs["height"]
-        self.beta_val = st.attrs["beta"]
-        self.r_0 = st.attrs["r_0"]
-        self.piercepoints = np.array(st.piercepoint)
-        self.mid_ra = st.attrs["midra"]
-        self.mid_dec = st.attrs["middec"]
+        self._adopt_screen_soltab(st, solset)
         self.ref_ind = ref_ind
         h5.close()
 
     def get_memory_usage(self, cellsize_deg, aterm_type="tec", n_freq=None):
-        """GB per time slot, stated as the reference states it for KL screens
-        (kl_screen.py:157-190: int() sizes, 8-byte values, /10 overhead,
-        x ncpu), for a [1, F, A, ny, nx] array ("gain": [1, F, A, 4, ny, nx])."""
-        ncpu = self.ncpu or multiprocessing.cpu_count()
-        ximsize = int(self.width_ra / cellsize_deg)
-        yimsize = int(self.width_dec / cellsize_deg)
-        n_f = len(self.freqs_ph) if n_freq is None else n_freq
-        planes = 4 if aterm_type == "gain" else 1
-        nbytes = 8 * n_f * len(self.station_names) * planes * yimsize * ximsize
-        return nbytes / 1024 ** 3 / 10 * ncpu
-
-    def evaluator(self, cellsize_deg):
-        key = float(cellsize_deg)
-        ev = self._evaluators.get(key)
-        if ev is None:
-            x, y = geometry.grid_coords(self.rad, self.dec, self.width_ra,
-                                        cellsize_deg, self.mid_ra, self.mid_dec)
-            ev = KLEvaluator(self.piercepoints, self.r_0, self.beta_val, x, y,
-                             self.device)
-            self._evaluators = {key: ev}
-        return ev
+        """GB per time slot (``_memory_usage``) for a [1, F, A, ny, nx] array
+        ("gain": [1, F, A, 4, ny, nx])."""
+        return self._memory_usage(
+            cellsize_deg, len(self.freqs_ph) if n_freq is None else n_freq,
+            4 if aterm_type == "gain" else 1)
 
     def make_matrix(self, t_start_index, t_stop_index, freq_ind, stat_ind,
                     cellsize_deg, out_dir=None, ncpu=0, aterm_type="tec"):
@@ -238,29 +196,18 @@ class KLTecScreen(Screen):
         """dTEC values of times [g_start, g_stop), all (freq, station): device
         batches of whole time rows in FITS byte order, NaN-scrubbed on the
         device, streamed through pinned buffers (as KLScreen.write_chunk)."""
-        from .streaming import PinnedPipeline
-        torch = __import__("torch")
         ev = self.evaluator(cellsize_deg)
-        vals = np.asarray(self.vals_ph)
-        n_f, n_a = vals.shape[1], vals.shape[2]
-        per_slot = 4 * ev.nx * ev.ny
-        row_bytes = n_f * n_a * per_slot
-        rows = max(1, int(max_batch_bytes // row_bytes))
-        rows = min(rows, g_stop - g_start)
-        coef = ev._upload(vals[g_start:g_stop])
-        # device buffers start 16-byte aligned: whole rows keep float4 stores
-        pipe = PinnedPipeline(torch, ev.dev, rows * row_bytes)
+        vals = np.asarray(self.vals_ph)[g_start:g_stop]
+        slots = vals.shape[1] * vals.shape[2]  # per time row
+        coef = ev._upload(vals)
         flags = SF_EVAL_NAN_SCRUB | SF_EVAL_BIG_ENDIAN
-        try:
-            for t0 in range(g_start, g_stop, rows):
-                t1 = min(g_stop, t0 + rows)
-                s0, s1 = (t0 - g_start) * n_f * n_a, (t1 - g_start) * n_f * n_a
-                slot, buf = pipe.device_buffer((s1 - s0) * per_slot)
-                out = buf.view(torch.float32).view(s1 - s0, ev.ny, ev.nx)
-                ev.values_device(coef[s0:s1], out, flags)
-                pipe.submit(slot, (s1 - s0) * per_slot, writer)
-        finally:
-            pipe.close()
+
+        def evaluate(r0, r1, buf):
+            out = buf.view(ev.torch.float32).view(-1, ev.ny, ev.nx)
+            ev.values_device(coef[r0 * slots:r1 * slots], out, flags)
+
+        stream_time_rows(writer, ev.dev, g_stop - g_start,
+                         slots * 4 * ev.nx * ev.ny, max_batch_bytes, evaluate)
 
     def write_chunk_gain(self, writer, g_start, g_stop, cellsize_deg, freqs_hz,
                          tec_to_phase, max_batch_bytes=1 << 30, fused="auto"):
@@ -273,51 +220,41 @@ class KLTecScreen(Screen):
         linear and the piercepoints are shared), then ``sf_kl_eval``.
         ``fused=True``: the TEC (and phase) coefficients uploaded once,
         ``sf_kl_eval_tec`` per batch.  ``"auto"``: ``fused_auto(D, F)``."""
-        from .streaming import PinnedPipeline
-        torch = __import__("torch")
         if fused not in (False, True, "auto"):
             raise ValueError(f'fused: {fused!r}, expected False, True or "auto"')
         ev = self.evaluator(cellsize_deg)
-        vals = np.asarray(self.vals_ph)
+        torch = ev.torch
+        vals = np.asarray(self.vals_ph)[g_start:g_stop]
         n_a, D = vals.shape[2], vals.shape[3]
         n_f = len(freqs_hz)
         if fused == "auto":
             fused = fused_auto(D, n_f)
         fidx = (np.zeros(n_f, int) if vals.shape[1] == 1 else
                 nearest_index(self.freqs_ph, freqs_hz))
-        per_slot = 16 * ev.nx * ev.ny
-        row_bytes = n_f * n_a * per_slot
-        rows = max(1, int(max_batch_bytes // row_bytes))
-        rows = min(rows, g_stop - g_start)
-        tec = torch.from_numpy(np.ascontiguousarray(vals[g_start:g_stop],
-                                                    np.float64)).to(ev.dev)
+        tec = ev._upload(vals, vals.shape)
         phi0 = None
         if self.vals_phi0 is not None:
-            phi0 = torch.from_numpy(np.ascontiguousarray(
-                self.vals_phi0[g_start:g_stop], np.float64)).to(ev.dev)
-        pipe = PinnedPipeline(torch, ev.dev, rows * row_bytes)
+            phi0 = np.asarray(self.vals_phi0)[g_start:g_stop]
+            phi0 = ev._upload(phi0, phi0.shape)
         flags = DEFAULT_FLAGS | SF_EVAL_NAN_SCRUB | SF_EVAL_BIG_ENDIAN
         rad_per_tecu = tec_to_phase / np.asarray(freqs_hz, np.float64)
         idx = torch.as_tensor(np.asarray(fidx, np.int64), device=ev.dev)
-        try:
-            for t0 in range(g_start, g_stop, rows):
-                t1 = min(g_stop, t0 + rows)
-                n = (t1 - t0) * n_f * n_a
-                sl = slice(t0 - g_start, t1 - g_start)
-                slot, buf = pipe.device_buffer(n * per_slot)
-                if fused:
-                    out = buf.view(torch.float32).view(t1 - t0, n_f, n_a, 4, ev.ny, ev.nx)
-                    ev.eval_tec_device(tec[sl], rad_per_tecu, fidx,
-                                       None if phi0 is None else phi0[sl], out, flags)
-                else:
-                    coef = tec_to_phase_coef(tec[sl], freqs_hz, tec_to_phase, fidx)
-                    if phi0 is not None:
-                        coef = coef + phi0[sl].index_select(1, idx)
-                    out = buf.view(torch.float32).view(n, 4, ev.ny, ev.nx)
-                    ev.eval_device(coef.view(n, D), out, flags)
-                pipe.submit(slot, n * per_slot, writer)
-        finally:
-            pipe.close()
+
+        def evaluate(r0, r1, buf):
+            sl = slice(r0, r1)
+            if fused:
+                out = buf.view(torch.float32).view(r1 - r0, n_f, n_a, 4, ev.ny, ev.nx)
+                ev.eval_tec_device(tec[sl], rad_per_tecu, fidx,
+                                   None if phi0 is None else phi0[sl], out, flags)
+            else:
+                coef = tec_to_phase_coef(tec[sl], freqs_hz, tec_to_phase, fidx)
+                if phi0 is not None:
+                    coef = coef + phi0[sl].index_select(1, idx)
+                out = buf.view(torch.float32).view(-1, 4, ev.ny, ev.nx)
+                ev.eval_device(coef.view(-1, D), out, flags)
+
+        stream_time_rows(writer, ev.dev, g_stop - g_start,
+                         n_f * n_a * 16 * ev.nx * ev.ny, max_batch_bytes, evaluate)
 
     def write(self, out_dir, cellsize_deg, aterm_type="tec",
               tec_to_phase=TEC_TO_PHASE, freqs_hz=None, ncpu=0, fused="auto"):
@@ -340,33 +277,17 @@ class KLTecScreen(Screen):
         gain = aterm_type == "gain"
         freqs = np.asarray(self.freqs_ph if freqs_hz is None or not gain else freqs_hz,
                            np.float64).reshape(-1)
-        gaps_ind = time_chunks(self.times_ph, self.get_memory_usage(
-            cellsize_deg, aterm_type, len(freqs)))
-        nx, ny = self.grid_size(cellsize_deg)
-        n_ant = len(self.station_names)
-        header = fits.aterm_header if gain else fits.tec_header
-        outfiles = []
-        g_start = 0
-        for gnum, g_stop in enumerate(gaps_ind):
-            outfile = os.path.join(out_dir, f"{self.name}_{gnum}.fits")
-            cards = header(self.rad, self.dec, nx, ny, cellsize_deg, freqs,
-                           self.times_ph[g_start:g_stop], n_ant)
-            shape = (g_stop - g_start, len(freqs), n_ant) + ((4,) if gain else ()) + (ny, nx)
-            writer = fits.CubeWriter(outfile, cards, shape)
-            try:
-                if gain:
-                    self.write_chunk_gain(writer, g_start, g_stop, cellsize_deg,
-                                          freqs, tec_to_phase, fused=fused)
-                else:
-                    self.write_chunk(writer, g_start, g_stop, cellsize_deg)
-            finally:
-                writer.close()
-            outfiles.append(outfile)
-            g_start = g_stop
-        with open(os.path.join(out_dir, f"{self.name}.txt"), "w",
-                  encoding="utf8") as fh:
-            fh.writelines([o + "\n" for o in outfiles])
-        return outfiles
+        mem = self.get_memory_usage(cellsize_deg, aterm_type, len(freqs))
+        if gain:
+            return self._write_cubes(
+                out_dir, cellsize_deg, mem, fits.aterm_header, freqs, (4,),
+                lambda writer, g_start, g_stop: self.write_chunk_gain(
+                    writer, g_start, g_stop, cellsize_deg, freqs, tec_to_phase,
+                    fused=fused))
+        return self._write_cubes(
+            out_dir, cellsize_deg, mem, fits.tec_header, freqs, (),
+            lambda writer, g_start, g_stop: self.write_chunk(
+                writer, g_start, g_stop, cellsize_deg))
 
 
 def make_tec_aterm_image(h5parmfile, soltabname="tec000", outroot="",
@@ -381,19 +302,9 @@ def make_tec_aterm_image(h5parmfile, soltabname="tec000", outroot="",
     ``phase_soltab_name``: the scalar-phase soltab of a tecandphase solution,
     added to the gain cube's phase.  Bounds and padding as
     ``make_aterm_image``.  Returns None."""
-    if isinstance(bounds_deg, str):
-        bounds_deg = [float(f.strip()) for f in bounds_deg.strip("[]").split(";")]
-    if isinstance(bounds_mid_deg, str):
-        bounds_mid_deg = [float(f.strip()) for f in bounds_mid_deg.strip("[]").split(";")]
-    bounds_deg = list(bounds_deg)
-    if padding_fraction is not None:
-        padding_fraction = float(padding_fraction)
-        padding_ra = (bounds_deg[2] - bounds_deg[0]) * (padding_fraction - 1.0)
-        padding_dec = (bounds_deg[3] - bounds_deg[1]) * (padding_fraction - 1.0)
-        bounds_deg[0] -= padding_ra
-        bounds_deg[1] -= padding_dec
-        bounds_deg[2] += padding_ra
-        bounds_deg[3] += padding_dec
+    from .make_aterm_images import padded_bounds
+    bounds_deg, bounds_mid_deg = padded_bounds(bounds_deg, bounds_mid_deg,
+                                               padding_fraction)
     cellsize_deg = float(cellsize_deg)
     width_deg = bounds_deg[3] - bounds_deg[1]
     screen = KLTecScreen(os.path.basename(outroot), h5parmfile, skymodel,

@@ -9,6 +9,28 @@ from .kl_screen import KLScreen
 from .voronoi_screen import VoronoiScreen
 
 
+def padded_bounds(bounds_deg, bounds_mid_deg, padding_fraction):
+    """The entry points' bounds arguments: ``bounds_deg`` [ra0, dec0, ra1,
+    dec1] and ``bounds_mid_deg`` [ra, dec], each a sequence or a string
+    "[a;b;...]", as lists of floats, ``bounds_deg`` grown on every side by
+    (``padding_fraction`` - 1) x its extent unless that is None.  A new list:
+    the reference pads the caller's in place."""
+    if isinstance(bounds_deg, str):
+        bounds_deg = [float(f.strip()) for f in bounds_deg.strip("[]").split(";")]
+    if isinstance(bounds_mid_deg, str):
+        bounds_mid_deg = [float(f.strip()) for f in bounds_mid_deg.strip("[]").split(";")]
+    bounds_deg = list(bounds_deg)
+    if padding_fraction is not None:
+        padding_fraction = float(padding_fraction)
+        padding_ra = (bounds_deg[2] - bounds_deg[0]) * (padding_fraction - 1.0)
+        padding_dec = (bounds_deg[3] - bounds_deg[1]) * (padding_fraction - 1.0)
+        bounds_deg[0] -= padding_ra
+        bounds_deg[1] -= padding_dec
+        bounds_deg[2] += padding_ra
+        bounds_deg[3] += padding_dec
+    return bounds_deg, bounds_mid_deg
+
+
 def make_aterm_image(h5parmfile, soltabname="phase000", screen_type="tessellated",
                      outroot="", bounds_deg=None, bounds_mid_deg=None,
                      skymodel=None, solsetname="sol000", padding_fraction=1.4,
@@ -21,19 +43,8 @@ def make_aterm_image(h5parmfile, soltabname="phase000", screen_type="tessellated
         soltab_amp = None
         soltab_ph = soltabname
 
-    if isinstance(bounds_deg, str):
-        bounds_deg = [float(f.strip()) for f in bounds_deg.strip("[]").split(";")]
-    if isinstance(bounds_mid_deg, str):
-        bounds_mid_deg = [float(f.strip()) for f in bounds_mid_deg.strip("[]").split(";")]
-    bounds_deg = list(bounds_deg)  # the reference pads the caller's list in place
-    if padding_fraction is not None:
-        padding_fraction = float(padding_fraction)
-        padding_ra = (bounds_deg[2] - bounds_deg[0]) * (padding_fraction - 1.0)
-        padding_dec = (bounds_deg[3] - bounds_deg[1]) * (padding_fraction - 1.0)
-        bounds_deg[0] -= padding_ra
-        bounds_deg[1] -= padding_dec
-        bounds_deg[2] += padding_ra
-        bounds_deg[3] += padding_dec
+    bounds_deg, bounds_mid_deg = padded_bounds(bounds_deg, bounds_mid_deg,
+                                               padding_fraction)
     cellsize_deg = float(cellsize_deg)
     smooth_deg = float(smooth_deg)
     smooth_pix = smooth_deg / cellsize_deg

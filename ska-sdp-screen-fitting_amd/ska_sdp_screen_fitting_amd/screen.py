@@ -205,20 +205,31 @@ class Screen:
     def write(self, out_dir, cellsize_deg, smooth_pix=0, ncpu=0):
         """Write the a-term screens to FITS cubes (screen.py:260-394)."""
         self.ncpu = ncpu
-        gaps_ind = time_chunks(self.times_ph, self.get_memory_usage(cellsize_deg))
+        return self._write_cubes(
+            out_dir, cellsize_deg, self.get_memory_usage(cellsize_deg),
+            fits.aterm_header, self.freqs_ph, (4,),
+            lambda writer, g_start, g_stop: self.write_chunk(
+                writer, g_start, g_stop, cellsize_deg, smooth_pix))
+
+    def _write_cubes(self, out_dir, cellsize_deg, mem_per_slot_gb, header, freqs,
+                     planes, write_chunk):
+        """``{name}_{g}.fits`` per time chunk (gap and memory chunking) and
+        ``{name}.txt`` listing them: cubes [time][freq][ant] + ``planes`` +
+        [y][x] with the cards of ``header`` (a ``fits`` header function),
+        filled by ``write_chunk(writer, g_start, g_stop)``."""
+        gaps_ind = time_chunks(self.times_ph, mem_per_slot_gb)
         nx, ny = self.grid_size(cellsize_deg)
+        n_ant = len(self.station_names)
         outfiles = []
         g_start = 0
         for gnum, g_stop in enumerate(gaps_ind):
             outfile = os.path.join(out_dir, f"{self.name}_{gnum}.fits")
-            cards = fits.aterm_header(self.rad, self.dec, nx, ny, cellsize_deg,
-                                      self.freqs_ph, self.times_ph[g_start:g_stop],
-                                      len(self.station_names))
-            shape = (g_stop - g_start, len(self.freqs_ph), len(self.station_names),
-                     4, ny, nx)
+            cards = header(self.rad, self.dec, nx, ny, cellsize_deg, freqs,
+                           self.times_ph[g_start:g_stop], n_ant)
+            shape = (g_stop - g_start, len(freqs), n_ant) + planes + (ny, nx)
             writer = fits.CubeWriter(outfile, cards, shape)
             try:
-                self.write_chunk(writer, g_start, g_stop, cellsize_deg, smooth_pix)
+                write_chunk(writer, g_start, g_stop)
             finally:
                 writer.close()
             outfiles.append(outfile)

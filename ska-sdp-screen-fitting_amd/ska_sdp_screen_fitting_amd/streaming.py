@@ -76,3 +76,29 @@ class PinnedPipeline:
         self.thread.join()
         if self.err is not None:
             raise self.err
+
+
+def batch_rows(n_rows, row_bytes, max_batch_bytes):
+    """Rows per device batch: the whole rows ``max_batch_bytes`` holds, at
+    least one, at most ``n_rows``."""
+    return min(max(1, int(max_batch_bytes // row_bytes)), n_rows)
+
+
+def stream_time_rows(writer, dev, n_rows, row_bytes, max_batch_bytes, evaluate):
+    """The loop of every ``write_chunk``: ``n_rows`` time rows of ``row_bytes``
+    each go to ``writer`` in batches of ``batch_rows`` rows.  For each batch
+    of rows [r0, r1), ``evaluate(r0, r1, buf)`` enqueues on the current stream
+    the kernels that fill ``buf``, the pipeline's uint8 device buffer of
+    exactly ``(r1 - r0) * row_bytes`` bytes (16-byte aligned: whole rows keep
+    float4 stores), in FITS byte order; it views ``buf`` as it needs."""
+    import torch
+    rows = batch_rows(n_rows, row_bytes, max_batch_bytes)
+    pipe = PinnedPipeline(torch, dev, rows * row_bytes)
+    try:
+        for r0 in range(0, n_rows, rows):
+            r1 = min(n_rows, r0 + rows)
+            slot, buf = pipe.device_buffer((r1 - r0) * row_bytes)
+            evaluate(r0, r1, buf)
+            pipe.submit(slot, (r1 - r0) * row_bytes, writer)
+    finally:
+        pipe.close()

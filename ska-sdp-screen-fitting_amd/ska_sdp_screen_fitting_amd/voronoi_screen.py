@@ -24,6 +24,7 @@ from . import fits, geometry
 from ._lib import SF_EVAL_BIG_ENDIAN, SF_EVAL_NAN_SCRUB, private_context
 from .h5parm import H5parm, get_reference_station
 from .screen import Screen, canonical_axes, phase_pols
+from .streaming import stream_time_rows
 
 
 def parse_angle(text, hours):
@@ -355,35 +356,28 @@ class VoronoiScreen(Screen):
         """Gather + smoothing of times [g_start, g_stop) in FITS byte order,
         streamed through pinned buffers (see streaming.py)."""
         import torch
-        from .streaming import PinnedPipeline
         dev, _ = self._device()
         ny, nx = self.data_rasertize_template.shape
-        n_f, n_a, D = self.vals_ph.shape[1:4]
-        per_slot = 16 * nx * ny
-        row_bytes = n_f * n_a * per_slot
-        rows = min(max(1, int(max_batch_bytes // row_bytes)), g_stop - g_start)
+        vals = self.vals_ph[g_start:g_stop]
+        slots = vals.shape[1] * vals.shape[2]  # per time row
         pyy = None
         if self.pol_phases:
-            ph = self._upload(self.vals_ph[g_start:g_stop, ..., 0])
-            pyy = self._upload(self.vals_ph[g_start:g_stop, ..., 1])
+            ph, pyy = self._upload(vals[..., 0]), self._upload(vals[..., 1])
         else:
-            ph = self._upload(self.vals_ph[g_start:g_stop])
+            ph = self._upload(vals)
         axx = ayy = None
         if not self.phase_only:
             amp = np.asarray(self.vals_amp)[g_start:g_stop]
             axx, ayy = self._upload(amp[..., 0]), self._upload(amp[..., 1])
-        pipe = PinnedPipeline(torch, dev, rows * row_bytes)
-        try:
-            for t0 in range(g_start, g_stop, rows):
-                t1 = min(g_stop, t0 + rows)
-                s0, s1 = (t0 - g_start) * n_f * n_a, (t1 - g_start) * n_f * n_a
-                slot, buf = pipe.device_buffer((s1 - s0) * per_slot)
-                out = buf.view(torch.float32).view(s1 - s0, 4, ny, nx)
-                self.eval_device(ph[s0:s1], out, smooth_pix,
-                                 SF_EVAL_NAN_SCRUB | SF_EVAL_BIG_ENDIAN,
-                                 amp_xx=None if axx is None else axx[s0:s1],
-                                 amp_yy=None if ayy is None else ayy[s0:s1],
-                                 phase_yy=None if pyy is None else pyy[s0:s1])
-                pipe.submit(slot, (s1 - s0) * per_slot, writer)
-        finally:
-            pipe.close()
+
+        def evaluate(r0, r1, buf):
+            s = slice(r0 * slots, r1 * slots)
+            out = buf.view(torch.float32).view(-1, 4, ny, nx)
+            self.eval_device(ph[s], out, smooth_pix,
+                             SF_EVAL_NAN_SCRUB | SF_EVAL_BIG_ENDIAN,
+                             amp_xx=None if axx is None else axx[s],
+                             amp_yy=None if ayy is None else ayy[s],
+                             phase_yy=None if pyy is None else pyy[s])
+
+        stream_time_rows(writer, dev, g_stop - g_start, slots * 16 * nx * ny,
+                         max_batch_bytes, evaluate)
