@@ -628,6 +628,39 @@ int sf_tess_fill_pol(sf_ctx* ctx, const int32_t* labels, int nx, int ny,
                      unsigned flags);
 
 /*
+ * Tessellated VALUE fill (tess_values.hip): one float32 plane per slot, the
+ * values themselves instead of their Jones terms.  Extends
+ * voronoi_screen.py:132-216 (VoronoiScreen.make_matrix) to values -- dTEC in
+ * TECU, or anything else solved per direction -- and gives the tessellated
+ * path the aterm_type="tec" cube of processing_utils.py:144-292; it is to
+ * sf_tess_fill what sf_kl_eval_values is to sf_kl_eval.  Device inputs:
+ * labels [ny][nx] int32 in 1..D (nx * ny < 2^31), values [S][D] float64
+ * (already referenced), 1 <= D <= SF_MAX_EVAL_DIR.  Device output
+ *   out[(s % ring_slots)][ny][nx] = g((float) values[s][labels[y][x] - 1])
+ * float32, g the identity (smooth_pix = 0) or the Gaussian of sf_smooth per
+ * image: float64 sums in scipy's order (centre first, then the pairs from the
+ * outermost inwards, no contraction), float32 between the y pass and the x
+ * pass, 'reflect' borders, truncated at 4 sigma -- where finite, bit for bit
+ * plane 0 of sf_tess_fill(phase = 0, amp_xx = values).  A label outside 1..D
+ * gives NaN and reads no table entry.  flags: SF_EVAL_NAN_SCRUB (NaN -> 0.0f
+ * after smoothing: the value sf_kl_eval_values scrubs to, whose Jones term is
+ * 1 / 0), SF_EVAL_BIG_ENDIAN, SF_EVAL_NT_STORES (honoured for 16-byte-aligned
+ * output and nx * ny % 4 == 0); any other bit is SF_EINVAL.  ring_slots in
+ * 1..INT32_MAX: with ring_slots < S an entry ends up holding the last slot
+ * that maps to it.  smooth_pix in [0, 1e4]: a radius int(4 smooth_pix + 0.5)
+ * <= 24 runs fused in one LDS-tiled kernel; a larger one gathers unscrubbed
+ * and then runs the two separable passes, which needs ring_slots >= S.  The
+ * output needs 4-byte alignment only (an unaligned output, or nx * ny % 4 !=
+ * 0, takes scalar stores).  S = 0 is a no-op.  SF_OPT_TESS_SLOTS and
+ * SF_OPT_TESS_WAVES are honoured by the unsmoothed fill.  Enqueued on the
+ * context stream; does not synchronise, except for the weight upload when
+ * smooth_pix changes (as sf_tess_fill).
+ */
+int sf_tess_fill_values(sf_ctx* ctx, const int32_t* labels, int nx, int ny,
+                        const double* values, int D, int64_t S, float* out,
+                        int64_t ring_slots, double smooth_pix, unsigned flags);
+
+/*
  * The Gaussian smoothing of Screen.write (screen.py:353-362:
  * scipy.ndimage.gaussian_filter(., sigma=(0, smooth_pix, smooth_pix)) per
  * image, float32 between the y and x passes, 'reflect' borders, truncate

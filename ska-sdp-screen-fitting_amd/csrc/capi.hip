@@ -913,6 +913,38 @@ int sf_tess_fill_pol(sf_ctx* ctx, const int32_t* labels, int nx, int ny,
   return sf::launch_smooth(ctx, out, nx, ny, S * 4, ctx->d_gw, R, flags);
 }
 
+int sf_tess_fill_values(sf_ctx* ctx, const int32_t* labels, int nx, int ny,
+                        const double* values, int D, int64_t S, float* out,
+                        int64_t ring, double smooth_pix, unsigned flags) {
+  SF_REQUIRE(ctx && labels && values && out, SF_EINVAL, "sf_tess_fill_values: NULL argument");
+  SF_REQUIRE(nx >= 1 && ny >= 1 && (int64_t)nx * ny <= INT32_MAX && D >= 1 &&
+                 D <= SF_MAX_EVAL_DIR && S >= 0 && ring >= 1 && ring <= INT32_MAX,
+             SF_EINVAL, "sf_tess_fill_values: bad shape");
+  SF_REQUIRE(smooth_pix >= 0.0 && smooth_pix <= 1e4, SF_EINVAL,
+             "sf_tess_fill_values: smooth_pix must be in [0, 1e4]");
+  SF_REQUIRE((reinterpret_cast<uintptr_t>(out) & 3) == 0, SF_EINVAL,
+             "sf_tess_fill_values: output not 4-byte aligned");
+  SF_REQUIRE((flags & ~(SF_EVAL_NAN_SCRUB | SF_EVAL_NT_STORES | SF_EVAL_BIG_ENDIAN)) == 0,
+             SF_EINVAL,
+             "sf_tess_fill_values: flags other than SF_EVAL_NAN_SCRUB, "
+             "SF_EVAL_NT_STORES and SF_EVAL_BIG_ENDIAN");
+  if (S == 0) return SF_OK;
+  SF_HIP(hipSetDevice(ctx->device));
+  int R = 0;
+  int rc = upload_gaussian(ctx, smooth_pix, &R);
+  if (rc != SF_OK) return rc;
+  if (R <= sf::kTessMaxR)
+    return sf::launch_tess_values(ctx, labels, nx, ny, values, D, S, out, ring, ctx->d_gw, R,
+                                  flags);
+  // wider Gaussians: gather unsmoothed and unscrubbed, then the two separable
+  // passes (scrub / byte swap after smoothing); every slot needs its own image
+  SF_REQUIRE(ring >= S, SF_EINVAL,
+             "sf_tess_fill_values: smooth_pix > 6 needs ring_slots >= S");
+  rc = sf::launch_tess_values(ctx, labels, nx, ny, values, D, S, out, ring, ctx->d_gw, 0, 0u);
+  if (rc != SF_OK) return rc;
+  return sf::launch_values_smooth(ctx, out, nx, ny, S, ctx->d_gw, R, flags);
+}
+
 int sf_smooth(sf_ctx* ctx, float* cube, int nx, int ny, int64_t n_img,
               double smooth_pix, unsigned flags) {
   SF_REQUIRE(ctx && cube && nx >= 1 && ny >= 1 && n_img >= 0, SF_EINVAL,

@@ -253,7 +253,7 @@ struct sf_ctx {
   double gw_sigma = -1.0;                // sigma whose weights d_gw holds
   sf::DevBuf<float> d_trash;  // 1 KiB sink of the eval's out-of-range stores
   sf::DevBuf<float> d_smooth;
-  sf::DevBuf<float> d_tess_tab;           // tessellated value table [S][D+1][4]
+  sf::DevBuf<float> d_tess_tab;           // tessellated value table [S][D+1][4] (value fill: [S][D+1])
   // fast-path switch (SCREENFIT_FIT=general forces the general kernel)
   int force_general = 0;
   // evaluation kernel (SF_OPT_EVAL_KERNEL)
@@ -365,4 +365,12 @@ int launch_tess_tile(sf_ctx* ctx, const int32_t* labels, int nx, int ny,
 int launch_smooth(sf_ctx* ctx, float* cube, int nx, int ny, int64_t n_img,
                   const double* d_w, int R, unsigned flags);
 constexpr int kTessMaxR = 24;  // Gaussian radius of the fused tess kernel
+// one-plane value fill (tess_values.hip): table pass + gather (R = 0) or the
+// fused tile kernel (R <= kTessMaxR); the two passes for any R over one-plane
+// images, scrubbing NaN to 0
+int launch_tess_values(sf_ctx* ctx, const int32_t* labels, int nx, int ny,
+                       const double* values, int D, int64_t S, float* out, int64_t ring,
+                       const double* d_w, int R, unsigned flags);
+int launch_values_smooth(sf_ctx* ctx, float* cube, int nx, int ny, int64_t n_img,
+                         const double* d_w, int R, unsigned flags);
 }  // namespace sf

@@ -18,3 +18,12 @@ def make_tec_aterm_image(*args, **kwargs):
     """See :func:`ska_sdp_screen_fitting_amd.kl_tec_screen.make_tec_aterm_image`."""
     from .kl_tec_screen import make_tec_aterm_image as _impl
     return _impl(*args, **kwargs)
+
+
+def __getattr__(name):
+    # the screen class of tessellated TEC screens, imported on first use (it
+    # pulls in scipy and Pillow, as the entry points above do)
+    if name == "VoronoiTecScreen":
+        from .voronoi_tec_screen import VoronoiTecScreen
+        return VoronoiTecScreen
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

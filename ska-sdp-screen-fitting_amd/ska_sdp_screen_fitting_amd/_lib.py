@@ -81,6 +81,7 @@ EXPORTED = (
     "sf_kl_eval_values",
     "sf_set_tec_freqs", "sf_kl_eval_tec",
     "sf_kl_eval_pol", "sf_tess_fill_pol",
+    "sf_tess_fill_values",
 )
 
 
@@ -180,6 +181,8 @@ def load_library(path=None):
                                c_int),
             "sf_tess_fill_pol": ([vp, vp, c_int, c_int, vp, vp, vp, vp, c_int, i64,
                                   vp, i64, c_dbl, ctypes.c_uint], c_int),
+            "sf_tess_fill_values": ([vp, vp, c_int, c_int, vp, c_int, i64, vp, i64,
+                                     c_dbl, ctypes.c_uint], c_int),
         }
         for name, (args, res) in sig.items():
             fn = getattr(lib, name)
@@ -574,6 +577,23 @@ class Context:
             self._dev(out, np.float32, self._out_numel(S, ring), "out"), ring,
             int(flags), self._dev(sums, np.int32, int(S), "sums")), "sf_kl_eval_sums")
 
+    def _validate_labels(self, labels, D):
+        """Labels in 1..D, checked once per label tensor OBJECT (held by a weak
+        reference, so a new tensor in the freed storage of the old one is
+        validated again), its in-place version and D: every chunk of a
+        Screen.write passes the same template, and min / max are two
+        reductions + two host syncs."""
+        if not (hasattr(labels, "min") and labels.numel()):
+            return
+        import weakref
+        prev = getattr(self, "_labels_ok", None)
+        key = (labels._version, int(D))
+        if prev is None or prev[0]() is not labels or prev[1] != key:
+            lo, hi = int(labels.min()), int(labels.max())
+            if lo < 1 or hi > int(D):
+                raise ValueError(f"labels: values {lo}..{hi} outside 1..{D}")
+            self._labels_ok = (weakref.ref(labels), key)
+
     def tess_fill(self, labels, nx, ny, phase, D, S, out, ring_slots=None,
                   amp_xx=None, amp_yy=None, smooth_pix=0.0,
                   flags=SF_EVAL_NAN_SCRUB, phase_yy=None):
@@ -581,20 +601,7 @@ class Context:
         take its cos / sin) sf_tess_fill_pol."""
         ring = max(int(S if ring_slots is None else ring_slots), 1)
         n = int(S) * int(D)
-        if hasattr(labels, "min") and labels.numel():
-            # validated once per label tensor OBJECT (held by a weak
-            # reference, so a new tensor in the freed storage of the old one
-            # is validated again), its in-place version and D: every chunk of
-            # a Screen.write passes the same template, and min / max are two
-            # reductions + two host syncs
-            import weakref
-            prev = getattr(self, "_labels_ok", None)
-            key = (labels._version, int(D))
-            if prev is None or prev[0]() is not labels or prev[1] != key:
-                lo, hi = int(labels.min()), int(labels.max())
-                if lo < 1 or hi > int(D):
-                    raise ValueError(f"labels: values {lo}..{hi} outside 1..{D}")
-                self._labels_ok = (weakref.ref(labels), key)
+        self._validate_labels(labels, D)
         _check(self.lib.sf_tess_fill_pol(
             self.h, self._dev(labels, np.int32, int(nx) * int(ny), "labels"),
             int(nx), int(ny), self._dev(phase, np.float64, n, "phase"),
@@ -604,6 +611,21 @@ class Context:
             self._dev(out, np.float32, min(int(S), ring) * 4 * int(nx) * int(ny), "out"),
             ring, float(smooth_pix), int(flags)), "sf_tess_fill")
 
+    def tess_fill_values(self, labels, nx, ny, values, D, S, out, ring_slots=None,
+                         smooth_pix=0.0, flags=SF_EVAL_NAN_SCRUB):
+        """sf_tess_fill_values: the values themselves, float32 [min(S, ring),
+        ny, nx] = g((float) values[s, labels - 1]), one plane per slot instead
+        of the 4 Jones planes (``values``: device [S, D] float64).  flags:
+        SF_EVAL_NAN_SCRUB (NaN -> 0, after smoothing), SF_EVAL_NT_STORES,
+        SF_EVAL_BIG_ENDIAN."""
+        ring = max(int(S if ring_slots is None else ring_slots), 1)
+        self._validate_labels(labels, D)
+        _check(self.lib.sf_tess_fill_values(
+            self.h, self._dev(labels, np.int32, int(nx) * int(ny), "labels"),
+            int(nx), int(ny), self._dev(values, np.float64, int(S) * int(D), "values"),
+            int(D), int(S),
+            self._dev(out, np.float32, min(int(S), ring) * int(nx) * int(ny), "out"),
+            ring, float(smooth_pix), int(flags)), "sf_tess_fill_values")
 
     def smooth(self, cube, nx, ny, n_img, smooth_pix, flags=0):
         """sf_smooth: Screen.write's Gaussian in place on n_img float32

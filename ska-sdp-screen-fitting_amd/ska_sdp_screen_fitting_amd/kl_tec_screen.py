@@ -295,18 +295,41 @@ def make_tec_aterm_image(h5parmfile, soltabname="tec000", outroot="",
                          solsetname="sol000", padding_fraction=1.4,
                          cellsize_deg=0.2, aterm_type="tec", ncpu=0,
                          tec_to_phase=TEC_TO_PHASE, freqs_hz=None, fused="auto",
-                         phase_soltab_name=None):
+                         phase_soltab_name=None, screen_type="kl", smooth_deg=0):
     """``make_aterm_image`` for a tec soltab: fit KL screens to it and write
     the dTEC cube (``aterm_type="tec"``) or the Jones cube at ``freqs_hz``
     (``"gain"``, see ``KLTecScreen.write`` for ``tec_to_phase`` and ``fused``).
     ``phase_soltab_name``: the scalar-phase soltab of a tecandphase solution,
-    added to the gain cube's phase.  Bounds and padding as
-    ``make_aterm_image``.  Returns None."""
+    added to the gain cube's phase.  ``screen_type="tessellated"`` renders the
+    solved values through the sky model's Voronoi cells instead
+    (``VoronoiTecScreen``; ``fused`` does not apply), smoothed by a Gaussian
+    of ``smooth_deg``; "kl" ignores ``smooth_deg``, and a soltab with one
+    direction is always tessellated -- both as ``make_aterm_image`` (Q14).
+    Bounds and padding as ``make_aterm_image``.  Returns None."""
     from .make_aterm_images import padded_bounds
+    if screen_type not in ("kl", "tessellated"):
+        raise ValueError(f"unknown screen_type {screen_type!r}")
     bounds_deg, bounds_mid_deg = padded_bounds(bounds_deg, bounds_mid_deg,
                                                padding_fraction)
     cellsize_deg = float(cellsize_deg)
     width_deg = bounds_deg[3] - bounds_deg[1]
+    # one direction forces the tessellated screen (Q14)
+    h5 = H5parm(h5parmfile)
+    if len(h5.get_solset(solsetname).get_soltab(soltabname).dir) == 1:
+        screen_type = "tessellated"
+    h5.close()
+    if screen_type == "tessellated":
+        from .voronoi_tec_screen import VoronoiTecScreen
+        screen = VoronoiTecScreen(os.path.basename(outroot), h5parmfile, skymodel,
+                                  bounds_mid_deg[0], bounds_mid_deg[1], width_deg,
+                                  width_deg, solset_name=solsetname,
+                                  tec_soltab_name=soltabname,
+                                  phase_soltab_name=phase_soltab_name)
+        screen.process(ncpu=ncpu)
+        screen.write(os.path.dirname(outroot), cellsize_deg,
+                     smooth_pix=float(smooth_deg) / cellsize_deg, aterm_type=aterm_type,
+                     tec_to_phase=tec_to_phase, freqs_hz=freqs_hz, ncpu=ncpu)
+        return
     screen = KLTecScreen(os.path.basename(outroot), h5parmfile, skymodel,
                          bounds_mid_deg[0], bounds_mid_deg[1], width_deg, width_deg,
                          solset_name=solsetname, tec_soltab_name=soltabname,
