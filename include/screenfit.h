@@ -104,7 +104,15 @@ typedef struct sf_fit_params {
   int ant_offset;   /* global index of this call's station 0 (ant shards) */
   const double* ref_phase; /* device [T][F][D] phases of the reference
                               station when it is not in this shard; NULL =
-                              read them from station ref_ant - ant_offset */
+                              read them from station ref_ant - ant_offset.
+                              SF_SCREEN_TEC with ref_ant == -1 is referenced
+                              to the LAST station of the whole soltab (quirk
+                              Q15): ref_phase holds that station's values;
+                              NULL = this call's last station, right only
+                              for an unsharded call or the shard that holds
+                              the global last station.  Never read for
+                              SF_SCREEN_AMPLITUDE, nor for SF_SCREEN_PHASE
+                              with ref_ant == -1 */
 } sf_fit_params;
 
 /* Library / device management */

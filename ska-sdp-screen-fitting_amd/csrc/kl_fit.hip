@@ -275,8 +275,9 @@ int launch_basis(sf_ctx* ctx) {
 
 // Referencing / ref-station skip parameters of one sf_kl_fit call
 // (stationscreen.py:994-997, :818), including the operator-precedence quirk
-// Q15 (tec is always referenced, to the last (local) station when
-// ref_ant == -1).
+// Q15 (tec is always referenced: with ref_ant == -1 to the last station of
+// the whole soltab, whose values a station shard passes as ref_phase; NULL =
+// the call's own last station).
 RefSpec ref_spec(const sf_fit_params* p, int A) {
   RefSpec r;
   const int ref = (p->ref_ant == -1) ? -1 : p->ref_ant - p->ant_offset;
@@ -286,8 +287,8 @@ RefSpec ref_spec(const sf_fit_params* p, int A) {
       if (p->ref_phase) r.refph = p->ref_phase; else r.sub = ref;
     }
   } else {
-    if (p->ref_ant == -1) r.sub = A - 1;
-    else if (p->ref_phase) r.refph = p->ref_phase;
+    if (p->ref_phase) r.refph = p->ref_phase;
+    else if (p->ref_ant == -1) r.sub = A - 1;
     else r.sub = ref;
   }
   if (ref >= 0 && ref < A) r.skip = ref;
